@@ -14,14 +14,20 @@ and exits with its code; under torchrun WORLD_SIZE must equal N.
     sequences are LPT-assigned to the ranks (spec_viterbi_amd.sharding), each rank runs its share,
     and the scores are gathered to rank 0 with one RCCL gather after the timed region.
 The timed region is bracketed by barrier + synchronize on every rank, the max over ranks is
-reported, and value = state-updates of all ranks / that time.  Every rank checks the reference
-file's rows of its timed output bit-exact against committed digests (tests/golden/
-score_digests.json: SHA-256 of the oracle's float32 rows), rank 0 also the gathered rows; a
-mismatch on any rank makes every rank exit non-zero.
+reported, and value = state-updates of all ranks / that time.
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` (the dominant kernel: HIP-event time on
-the stream it runs on; VALU-issue utilisation and HBM bytes from rocprofv3 PMC passes this script
-runs as child processes on tools/launch.py with the same workload), `timing` (setup-inclusive and
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm
+up, time `--steps` passes, write the last pass's outputs with `--dump-outputs DIR` (scores.npy,
+best_states.npy, with --paths also paths.npy and path_offsets.npy; the inputs are the same in
+every run with the same arguments) and print metric / value / ms_per_step, the config and the
+HIP-event `timing.kernel_ms` of the timed passes.
+
+`--full` adds everything else.  Every rank checks the reference file's rows of its timed output
+bit-exact against committed digests (tests/golden/score_digests.json: SHA-256 of the oracle's
+float32 rows), rank 0 also the gathered rows; a mismatch on any rank makes every rank exit
+non-zero.  Extra objects: `roofline` (the dominant kernel: HIP-event time on the stream it runs
+on; VALU-issue utilisation and HBM bytes from rocprofv3 PMC passes this script runs as child
+processes on tools/launch.py with the same workload), the rest of `timing` (setup-inclusive and
 host-to-host rates) and `cpu_baseline` (the oracle on this host's cores).
 """
 from __future__ import annotations
@@ -68,10 +74,21 @@ def parse(argv=None):
     p.add_argument("--replicate", type=int, default=1,
                    help="batch = the file's sequences plus R-1 same-shape synthetic copies per GPU (full-chip "
                         "weak scaling, SURVEY 8(e): emit_50 x 8k sequences = --replicate 160); 1 = the headline")
+    p.add_argument("--full", action="store_true",
+                   help="also everything beyond the headline figure: the golden check of the timed output, setup and "
+                        "host-to-host timings, the roofline (rocprofv3 PMC child passes, the latency plan's floor) and "
+                        "the CPU baseline; --no-cpu-baseline / --no-pmc / --no-check / --cpu-seconds refine it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy: scores (float32), "
+                        "best_states (float64), with --paths also paths (float64, the sequences' paths end to end); "
+                        "ranks > 0 write <name>_rank<r>.npy; outputs over 64 MB in all: a fixed seeded sample of rows")
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU: exercise the launcher / rendezvous / timing scaffolding over gloo (CPU tests)")
     p.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- multi-process launch ----------------------------------------------------------------------
@@ -418,6 +435,35 @@ def check_rows(scores, best, index, ref_rows) -> list[int]:
     return bad
 
 
+DUMP_LIMIT = 64 << 20  # bytes of .npy data per --dump-outputs directory
+
+
+def dump_outputs(dirname: str, rank: int, scores, best, paths=None) -> None:
+    """--dump-outputs: the arrays of the last timed step as DIR/<name>.npy (rank 0) or
+    DIR/<name>_rank<r>.npy: scores float32 [rows, n], best_states float64 [rows], with paths the
+    rows' decoded paths end to end as float64 (and path_offsets, where row k's path starts).  Over
+    DUMP_LIMIT bytes: the same seeded sample of rows in every run, sorted, listed in rows.npy."""
+    scores = np.asarray(scores, np.float32)
+    nrows = scores.shape[0]
+    per_row = scores.shape[1] * 4 + 8 + 8
+    if paths is not None:
+        per_row += 8 + 8 * max((int(p.size) for p in paths), default=0)
+    keep = None
+    if nrows * per_row > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(20240607).choice(nrows, size=max(1, DUMP_LIMIT // per_row), replace=False))
+    sel = np.arange(nrows) if keep is None else keep
+    arrays = {"scores": np.ascontiguousarray(scores[sel]), "best_states": np.asarray(best)[sel].astype(np.float64)}
+    if keep is not None:
+        arrays["rows"] = keep.astype(np.float64)
+    if paths is not None:
+        picked = [np.asarray(paths[k]) for k in sel]
+        arrays["paths"] = (np.concatenate(picked) if picked else np.zeros(0)).astype(np.float64)
+        arrays["path_offsets"] = np.concatenate([[0], np.cumsum([p.size for p in picked])]).astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def all_ok(ok: bool, world, local, args) -> bool:
     """Logical AND over ranks (every rank learns whether any rank failed its check)."""
     if world == 1:
@@ -468,7 +514,7 @@ def main(argv=None):
     # setup (svh_model_create: host CSR + plans + upload), the counterpart of the per-call model
     # build the reference times inside run_Viterbi (bench_Viterbi.h:53-56, GraphBLAS_impl.cpp:9-54)
     setup = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         t0 = time.perf_counter()
         m = svh.DeviceModel(hmm, device=local, kernel=args.kernel, max_threads=args.max_threads)
         setup.append(time.perf_counter() - t0)
@@ -516,22 +562,29 @@ def main(argv=None):
     elapsed = max_over_ranks(time.perf_counter() - t0, world, local, args)
     kernel_ms = float(ev_start.elapsed_time(ev_stop)) / max(args.steps, 1)
 
-    scores, best = batch.read(sptr) if batch else (np.zeros((0, n), np.float32), np.zeros(0, np.int64))
+    scores, best, paths = np.zeros((0, n), np.float32), np.zeros(0, np.int64), None
+    if batch and args.paths and args.dump_outputs:
+        scores, best, paths = batch.read(sptr, want_paths=True)
+    elif batch:
+        scores, best = batch.read(sptr)
+    if args.dump_outputs and not (strong and world > 1):
+        dump_outputs(args.dump_outputs, rank, scores, best, paths)
     # rows of the last timed pass the pipelined kernel handed to the serial kernel (0 expected)
     fallbacks = batch.fallbacks() if batch else 0
     # correctness guard on the timed output: every rank checks the reference file's rows it ran
     # against the committed digests (level <= 1: score_digests.json's non-spec rows; level 2 on the
     # headline file: its level-2 rows, all 50, tests/golden/make_golden.py spec2)
     golden_checked, bad = False, []
-    ref_rows = digest_rows(args.model, ess_name)
-    spec_rows = digest_rows(args.model, f"{ess_name} level {args.level}") if args.level >= 2 else None
-    if not args.no_check and args.level <= 1 and ref_rows is not None:
+    check = args.full and not args.no_check  # the comparison with the reference's rows: --full only
+    ref_rows = digest_rows(args.model, ess_name) if check else None
+    spec_rows = digest_rows(args.model, f"{ess_name} level {args.level}") if check and args.level >= 2 else None
+    if check and args.level <= 1 and ref_rows is not None:
         bad = check_rows(scores[: len(file_index)], best[: len(file_index)], file_index, ref_rows)
         golden_checked = True
-    elif not args.no_check and args.level >= 2 and spec_rows is not None:
+    elif check and args.level >= 2 and spec_rows is not None:
         bad = check_rows(scores[: len(file_index)], None, file_index, spec_rows)
         golden_checked = True
-    if not all_ok(not bad, world, local, args):
+    if check and not all_ok(not bad, world, local, args):
         if bad:
             sys.stderr.write(f"bench.py: rank {rank}: timed output differs from the golden digests in rows {bad[:10]}\n")
         return 1
@@ -542,10 +595,12 @@ def main(argv=None):
         gbest = _gather_rows(assignment, np.asarray(best, np.int64).reshape(-1, 1), len(file_seqs), -1,
                              device=f"cuda:{local}")
         gather_ms = (time.perf_counter() - t_g) * 1e3
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, 0, gathered, gbest.reshape(-1))
         gbad = []
-        if rank == 0 and not args.no_check and args.level <= 1 and ref_rows is not None:
+        if rank == 0 and check and args.level <= 1 and ref_rows is not None:
             gbad = check_rows(gathered, gbest.reshape(-1), range(len(file_seqs)), ref_rows)
-        if not all_ok(not gbad, world, local, args):
+        if check and not all_ok(not gbad, world, local, args):
             if gbad:
                 sys.stderr.write(f"bench.py: gathered rows differ from the golden digests: {gbad[:10]}\n")
             return 1
@@ -563,7 +618,7 @@ def main(argv=None):
     # what svh_reader_next yields; svh_viterbi_u8: H2D, run, D2H of scores and best states), and
     # from the reader's list of uint64 arrays (svh_viterbi_seqs, narrowed on the host per call)
     e2e_ms = e2e_list_ms = e2e_pageable_ms = None
-    if rank == 0 and seqs and not strong:
+    if args.full and rank == 0 and seqs and not strong:
         from spec_viterbi_amd.hmm import pack_sequences
         offs, sym64 = pack_sequences(seqs)
         sym8 = sym64.astype(np.uint8)
@@ -594,7 +649,7 @@ def main(argv=None):
                  else "spec_chunk+" + KERNEL_NAMES.get(plan["kernel"], "?") if args.level >= 2
                  else KERNEL_NAMES.get(plan["kernel"], "?"))
         pmc = None
-        if not args.no_pmc and world == 1 and (args.level <= 1 or spec2 or l2pipe) and plan["kernel"] in (4, 5, 6, 7, 8, 9):
+        if args.full and not args.no_pmc and world == 1 and (args.level <= 1 or spec2 or l2pipe) and plan["kernel"] in (4, 5, 6, 7, 8, 9):
             # the dominant kernel's counters (with --paths: the pipelined kernel's PATHS variant, the
             # pass's dominant kernel; its traceback and the exiting chain launch are not counted;
             # level 2: the on-chip chunk kernel, not the step kernels' one-observation tails)
@@ -613,9 +668,9 @@ def main(argv=None):
             ess_b = essential_bytes_per_launch(n, int(info["S"]), lengths, False)
         else:
             ess_b = algo if args.level >= 2 else essential_bytes_per_launch(n, int(info["S"]), lengths, args.paths)
-        rl = roofline(info, plan, len(seqs), kernel_ms, algo, pmc, ess_b, max(lengths) - 1)
+        rl = roofline(info, plan, len(seqs), kernel_ms, algo, pmc, ess_b, max(lengths) - 1) if args.full else None
         floor_ms = None
-        if plan["kernel"] == 5 and not args.paths and args.level <= 1 and batch:
+        if args.full and plan["kernel"] == 5 and not args.paths and args.level <= 1 and batch:
             # the latency plan's own floor, measured live: the same launch with every boundary exchange
             # removed (svh_batch_step_floor_ms: each wave sweeps its block with no neighbour input and no
             # waits), i.e. the step's per-observation issue time at one wave per SIMD plus the prologue
@@ -665,8 +720,11 @@ def main(argv=None):
                 "parallelism": (f"LPT sequence shards x{world}, one RCCL gather of scores after timing" if strong
                                 else f"sequence-sharded x{world} (one process per GPU, no collective)"),
             },
-            "timing": {
-                "kernel_ms": round(kernel_ms, 4),
+            "timing": {"kernel_ms": round(kernel_ms, 4),
+                       "gather_ms": round(gather_ms, 3) if gather_ms is not None else None},
+        }
+        if args.full:  # what took runs of its own: setup and host-to-host timings, roofline, CPU baseline
+            out["timing"].update({
                 "setup_ms": round(float(np.median(setup)) * 1e3, 3),
                 "e2e_ms_per_step": None if e2e_ms is None else round(e2e_ms, 3),
                 "e2e_over_kernel_ms": None if e2e_ms is None else round(e2e_ms - kernel_ms, 3),
@@ -675,7 +733,6 @@ def main(argv=None):
                 "e2e_M_state_updates_per_s": None if not e2e_ms else round(updates_per_rank / e2e_ms / 1e3, 2),
                 "setup_plus_e2e_M_state_updates_per_s": None if not e2e_ms else
                 round(updates_per_rank / (e2e_ms + float(np.median(setup)) * 1e3) / 1e3, 2),
-                "gather_ms": round(gather_ms, 3) if gather_ms is not None else None,
                 "note": "setup_ms = svh_model_create (host CSR + plans + upload; the reference rebuilds its model inside "
                         "every run_Viterbi call, bench_Viterbi.h:53-56); e2e = svh_viterbi_u8 from host symbols in the device "
                         "format (packed uint8, as svh_reader_next yields them) to host scores and best states in "
@@ -683,10 +740,9 @@ def main(argv=None):
                         "on rank 0; e2e_pageable_out = the same into fresh numpy arrays (staged D2H + copy-out); "
                         "e2e_list_u64 = from the reader's list of uint64 arrays (svh_viterbi_seqs, narrowed per "
                         "call), pageable outputs",
-            },
-            "roofline": rl,
-        }
-        if not args.no_cpu_baseline and world == 1 and args.level <= 1:
+            })
+            out["roofline"] = rl
+        if args.full and not args.no_cpu_baseline and world == 1 and args.level <= 1:
             out["cpu_baseline"] = cpu_baseline(hmm, file_seqs, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if batch:

@@ -9,6 +9,7 @@ Floats are stored as IEEE-754 bit patterns (hex) so the vectors are exact.
     python tests/golden/make_golden.py spec2      # + level-2 digests of every emit_50 row (config 4)
     python tests/golden/make_golden.py scope      # scope_digests.json: every .chmm x emit_3_3500_20
     python tests/golden/make_golden.py sweep2     # sweep2_digests.json: level 2 of the sweep's other files
+    python tests/golden/make_golden.py readers    # reader_ref_digests.json: the reference reader's parse of every file
 """
 from __future__ import annotations
 
@@ -182,7 +183,30 @@ def sweep2_digests():
         print("sweep2", name, flush=True)
 
 
+def reader_digests():
+    """What the reference's own reader (oracle/_ref/ref_reader_dump, built by `make ref` where the
+    reference checkout is present) prints for every .chmm and .ess under data/: the SHA-256 of its
+    whitespace-separated tokens joined by single blanks, keyed by the path below data/, in
+    reader_ref_digests.json.  tests/test_reader_ref.py checks the engine's reader against them."""
+    import glob
+    import hashlib
+    import subprocess
+
+    ref = os.path.join(ROOT, "oracle", "_ref", "ref_reader_dump")
+    out = {}
+    for kind, sub in (("chmm", "chmm_files"), ("ess", "ess_files")):
+        for f in sorted(glob.glob(os.path.join(DATA, sub, "**", "*." + kind), recursive=True)):
+            toks = subprocess.run([ref, kind, f], capture_output=True, text=True, check=True).stdout.split()
+            out[os.path.relpath(f, DATA)] = hashlib.sha256(" ".join(toks).encode()).hexdigest()
+    with open(os.path.join(OUT, "reader_ref_digests.json"), "w") as fh:
+        json.dump(out, fh, indent=0, sort_keys=True)
+    print("reader digests", len(out))
+
+
 def main():
+    if sys.argv[1:] == ["readers"]:
+        reader_digests()
+        return
     if sys.argv[1:] == ["scope"]:
         scope_digests()
         return

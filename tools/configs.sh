@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/configs}
 mkdir -p "$OUT"
-B="timeout -k 10 300 python bench.py --no-cpu-baseline"
+B="timeout -k 10 300 python bench.py --full --no-cpu-baseline"
 $B --model 100.chmm --ess emit_3_3500_20.ess --steps 50 > "$OUT/c2_100_emit3.json" 2> "$OUT/c2.err" &&
 $B --steps 20 > "$OUT/c3_2405_emit50.json" 2> "$OUT/c3.err" &&
 $B --steps 10 --paths > "$OUT/c3_2405_emit50_paths.json" 2> "$OUT/c3p.err" &&

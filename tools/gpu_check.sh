@@ -7,13 +7,14 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 TAG=${TAG:-r03}
 TESTS=${TESTS:-tests}
-mkdir -p gpurun_out
+OUT=${OUT:-out}
+mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest $TESTS -v -m gpu --maxfail=20 --timeout 120 --timeout-method thread \
-    > gpurun_out/pytest_gpu_${TAG}.log 2>&1
+    > "$OUT/pytest_gpu_${TAG}.log" 2>&1
 rc=$?
-tail -3 gpurun_out/pytest_gpu_${TAG}.log
+tail -3 "$OUT/pytest_gpu_${TAG}.log"
 case $rc in 124|134|137|139) echo "pytest ended with $rc: stopping"; exit $rc;; esac
-timeout -k 10 300 python bench.py > gpurun_out/bench_${TAG}.log 2>&1 || exit $?
-tail -1 gpurun_out/bench_${TAG}.log | cut -c1-400
+timeout -k 10 300 python bench.py --full > "$OUT/bench_${TAG}.log" 2>&1 || exit $?
+tail -1 "$OUT/bench_${TAG}.log" | cut -c1-400
 if [ -z "$NO_PROFILE" ]; then TAG=$TAG bash tools/profile.sh || exit $?; fi
 exit $rc

@@ -9,10 +9,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 bash tools/gpu_session.sh $OUT || exit 1
 OUT=$OUT/configs bash tools/configs.sh > /dev/null || exit 1
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-pmc --steps 20 --replicate 2 > $OUT/configs/c3_2405_emit50_x2_latency.json 2> $OUT/configs/c3x2.err || exit 1
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-pmc --steps 20 --replicate 2 > $OUT/configs/c3_2405_emit50_x2_latency.json 2> $OUT/configs/c3x2.err || exit 1
 for w in headline:"" paths:"--paths" level2:"--level 2"; do
   name=${w%%:*}; args=${w#*:}
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$name -o run -- python3 bench.py --steps 20 --warmup 3 --no-pmc --no-cpu-baseline $args > $OUT/prof_$name.json 2> $OUT/prof_$name.err || exit 1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$name -o run -- python3 bench.py --full --steps 20 --warmup 3 --no-pmc --no-cpu-baseline $args > $OUT/prof_$name.json 2> $OUT/prof_$name.err || exit 1
 done
 for f in $OUT/configs/*.json; do python3 -c "
 import json,sys

@@ -11,7 +11,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 TAG=${TAG:-r03}
 OUT=gpurun_out/prof_${TAG}
-ARGS=${BENCH_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline --no-pmc"}
+ARGS=${BENCH_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc"}
 mkdir -p "$OUT"
 echo 'pmc: GRBM_GUI_ACTIVE' > "$OUT/trace.txt"
 echo 'pmc: FETCH_SIZE' > "$OUT/fetch.txt"
