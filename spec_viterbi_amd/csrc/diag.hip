@@ -23,20 +23,24 @@
 //     32 columns, one refilled per block of 32 steps, two groups ahead of use (global loads one block
 //     before their LDS writes; one s_barrier per block), so a block's last steps can read the next
 //     block's first pairs ahead of time;
-//   * the uniform constants of o_t: a per-wave stream in LDS, one 32-byte entry per step
-//     {A_F, A_S, X_FF, X_SF, X_SS, ring address of (o_t, step)}, built one block ahead from the
-//     sequence's symbols (two broadcast reads per step).
-// The steps are software-pipelined: a stream entry is read kPS steps and a ring pair kPE steps
-// before its use (the ring address comes from the stream), across block boundaries too.
+//   * the uniform values of o_t: per-wave streams in LDS, built one block ahead from the sequence's
+//     symbols: the constants {A_F, A_S, X_FF, X_SS}, 16 bytes per step (one broadcast ds_read_b128);
+//     the ring address of (o_t, step), 4 bytes per step, read four steps at a time (one
+//     ds_read_b128); and, for models whose S takes a term from F (SX), X_SF likewise.
+// The steps are software-pipelined: a step's constants are read kPS steps, its ring address eight to
+// eleven steps and its ring pair kPE steps before their use, across block boundaries too; the reads
+// of two steps are issued together, so that one counted wait serves both.
 // A workgroup is W sequences x one range of 64 diagonals: its waves walk the same ring columns
 // (shared ring), each with its own sequence's symbols.
 // Per step and lane (wave64):  Y = {x, x} + {A_F, A_S};  W = {F, F} + {X_FF, X_SF};
 //   Z = {ea, eb} + {F, x};  x' = min(Z.eb, Z.ea);  c' = min(fl(X_SS + c), Y.A_S, W.X_SF);
-//   viol += [Y.A_F < W.X_FF];  F' = W.X_FF
-// -- three v_pk_add_f32, five VALU more, three LDS reads.  The sink S and the violation check
-// are lane-local exactly as in pipe_kernel.h (S(t) = min over lanes of a per-lane recurrence driven
-// by the lane's own scores: fl(a + .) is monotone; the lane holding the S(0) chain is range 0's
-// lane 0).  F' is computed by every wave redundantly (the same operations: bit-identical).
+//   EXEC &= ![Y.A_F < W.X_FF];  F' = W.X_FF
+// -- two v_pk_add_f32 (three with SX), five VALU more (an address add among them; the check is one
+// v_cmpx: a lane that fails it switches itself off until the block's end, where the wave notes which
+// lanes are left) and 2.25 LDS reads (2.5 with SX).  The sink S and the violation check are
+// lane-local exactly as in pipe_kernel.h (S(t) = min over lanes of a per-lane recurrence driven by
+// the lane's own scores: fl(a + .) is monotone; the lane holding the S(0) chain is range 0's lane 0).
+// F' is computed by every wave redundantly (the same operations: bit-identical).
 // The last wave of a sequence to finish combines the ranges' partials (S, argmin, violation); a
 // row whose check failed is re-run exactly by that wave's workgroup (pipe_rerun_row) in the same
 // launch.
@@ -57,7 +61,8 @@ constexpr uint32_t kDR = 5 * kDK;     // ring columns (five groups of kDK)
 constexpr uint32_t kDRS = kDR + 64;   // slots per symbol plane: the ring and a mirror of its first 64
 constexpr uint32_t kDG = kDR / kDK;   // ring groups
 constexpr uint32_t kCP = kDK / 2;     // 16-byte chunks of a plane's group (two columns each)
-constexpr uint32_t kDE = 8;           // floats per stream entry
+constexpr uint32_t kDE = 4;           // floats per entry of the constants stream
+constexpr uint32_t kAG = 4;           // steps per read of the address stream and of the X_SF stream
 #ifndef SVH_DIAG_PS
 #define SVH_DIAG_PS 6
 #endif
@@ -67,8 +72,12 @@ constexpr uint32_t kDE = 8;           // floats per stream entry
 constexpr uint32_t kPS = SVH_DIAG_PS;  // steps a stream entry is read ahead of its use (two at a time)
 constexpr uint32_t kPE = SVH_DIAG_PE;  // steps a ring pair is read ahead of its use (< kPS)
 constexpr uint32_t kNS = kPS + 2;      // stream registers: entries j .. j + kPS - 1 and the two being read
-static_assert(kPE < kPS && kPS % 2 == 0 && kDK % kNS == 0 && kDK % kPE == 0,
-              "prefetch distances: the register slots of step j (j % kNS, j % kPE) repeat every block");
+constexpr uint32_t kNE = kPE + 2;      // ring-pair registers: pairs j .. j + kPE - 1 and the two being read
+static_assert(kPE + 2 <= kPS && kPS % 2 == 0 && kPE % 2 == 0 && kDK % kNS == 0 && kDK % kNE == 0,
+              "prefetch distances: the register slots of step j (j % kNS, j % kNE) repeat every block");
+static_assert(kPE == 2 && kDK % (2 * kAG) == 0,
+              "address groups: read 2 kAG steps ahead into two register slots (group % 2), which repeat every block; "
+              "a group's slot is free once the pairs of its last two steps are issued (kPE = 2)");
 constexpr uint32_t kDMaxSym = 32;
 // SVH_DIAG_AB (diagnostic builds, timing only, wrong results): 1 = no stream reads in the steps
 // (every step takes the block's first entry), 2 = no ring reads (the prologue's pairs), 3 = no
@@ -88,19 +97,36 @@ __device__ __forceinline__ f2 lds_ld2(uint32_t a) {
     return *(const __attribute__((address_space(3))) f2*)(size_t)a;
 }
 
-// viol += [a < b]: the compare into VCC and v_addc with VCC as the carry-in (two VALU; the compiler's
-// compare / v_cndmask / add needs a wait state besides)
-__device__ __forceinline__ void push_lt(uint32_t& acc, float a, float b) {
-    asm volatile("v_cmp_lt_f32_e32 vcc, %1, %2\n\t"
-                 "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc"
-                 : "+v"(acc)
-                 : "v"(a), "v"(b)
-                 : "vcc");
+// The speculation check, one VALU: EXEC &= !(a < b) (v_cmpx writes VCC and EXEC).  A lane whose
+// check fails switches itself off and stays off until its wave's next exec_collect(): what it
+// would have computed is never used, its row is re-run exactly (pipe_rerun_row overwrites every
+// score of the row), so only the fact that it failed has to survive.  !(a < b) keeps a lane on
+// where a or b is a NaN, as [a < b] counted nothing there.
+// EXEC is not in the clobber list: the compiler reserves it, rejects it there with a warning and
+// keeps nothing in it across straight-line code; the steps between two exec_collect() calls are
+// straight-line code or a wave-uniform loop (scalar branches), and the scheduler is fenced off at
+// both ends (sched_barrier), so that no lane-wise work of the all-lanes code around them (the
+// cooperative ring refill above all) lands among instructions that some lanes skip.
+__device__ __forceinline__ void check_off(float a, float b) {
+    asm volatile("v_cmpx_nlt_f32_e32 vcc, %0, %1" : : "v"(a), "v"(b) : "vcc");
+}
+// alive &= EXEC; EXEC = all lanes.  s_nop 4: five wait states between a write of EXEC and a DPP
+// operation (the epilogue's reductions; the compiler does not see this write).
+__device__ __forceinline__ void exec_collect(uint64_t& alive) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_and_b64 %0, %0, exec\n\t"
+                 "s_mov_b64 exec, -1\n\t"
+                 "s_nop 4"
+                 : "+s"(alive)
+                 :
+                 : "scc", "memory");
+    __builtin_amdgcn_sched_barrier(0);
 }
 
-__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S) {
-    // ring [S][kDRS] float2 | symbol template [S][8] | streams [W][2][kDK][kDE] | blocks [W] | rerun rows [W]
-    return ((size_t)S * kDRS * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * kDE + 2 * W) * 4;
+__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx) {
+    // ring [S][kDRS] float2 | symbol template [S][8] | constants [W][2][kDK][kDE] | ring addresses [W][2][kDK] |
+    // X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
+    return ((size_t)S * kDRS * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
 }
 
 template <int W, bool SX>
@@ -110,8 +136,10 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     const uint32_t S = m.S, NR = m.nrng, NP = NR * 64, P = m.P;
     float* ring = lds;                                   // [S][kDRS] {ea, eb}
     float* hcr = ring + (size_t)S * kDRS * 2;            // [S][8] stream template of symbol o
-    float* strm = hcr + S * 8;                           // [W][2][kDK][kDE]
-    uint32_t* wnb = reinterpret_cast<uint32_t*>(strm + W * 2 * kDK * kDE);  // [W] blocks of wave w
+    float* strm = hcr + S * 8;                           // [W][2][kDK] {A_F, A_S, X_FF, X_SS}
+    float* adr = strm + W * 2 * kDK * kDE;               // [W][2][kDK] ring address of (o_t, step)
+    float* xsf = adr + W * 2 * kDK;                      // [W][2][kDK] X_SF (SX only)
+    uint32_t* wnb = reinterpret_cast<uint32_t*>(xsf + (SX ? W * 2 * kDK : 0));  // [W] blocks of wave w
     uint32_t* rrow = wnb + W;                            // [W] row wave w's combine hands to the re-run
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -191,12 +219,12 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         if (lane < kDK) {
             const uint32_t o = symv < S ? symv : 0u;
             const float4 h0 = *reinterpret_cast<const float4*>(hcr + o * 8);
-            float4 h1 = *reinterpret_cast<const float4*>(hcr + o * 8 + 4);
+            const float2 h1 = *reinterpret_cast<const float2*>(hcr + o * 8 + 4);
             const uint32_t i = kb * kDK + 1 + lane;
-            h1.y = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + (i % kDR) * 8u);
-            float* d = strm + ((w * 2 + (kb & 1u)) * kDK + lane) * kDE;
-            *reinterpret_cast<float4*>(d) = h0;
-            *reinterpret_cast<float4*>(d + 4) = h1;
+            const uint32_t e = (w * 2 + (kb & 1u)) * kDK + lane;
+            *reinterpret_cast<float4*>(strm + e * kDE) = h0;
+            adr[e] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + (i % kDR) * 8u);
+            if (SX) xsf[e] = h1.x;
         }
     };
 
@@ -222,7 +250,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
 
     // ---- state at observation first - 1
     float xv = kInf, F = kInf, c = kInf;
-    uint32_t viol = 0;
+    uint64_t alive = ~0ull;  // lanes whose check has held so far (collected from EXEC after every block)
     if (real && beg == 0) {
         const uint32_t o0 = (uint32_t)uniform((int)sym[0]);
         const uint32_t p = rg * 64 + lane;
@@ -242,51 +270,64 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     for (int u = 0; u < W; ++u) nbmax = wnb[u] > nbmax ? wnb[u] : nbmax;
     nbmax = (uint32_t)uniform((int)nbmax);
 
-    // software pipeline: stream entries of steps j .. j + kPS + 1 and ring pairs of j .. j + kPE - 1
-    // in registers (slot j % kNS, j % kPE)
+    // software pipeline: stream entries of steps j .. j + kPS + 1 and ring pairs of j .. j + kPE + 1
+    // in registers (slot j % kNS, j % kNE)
     typedef float hvec __attribute__((ext_vector_type(4 * kNS)));
-    typedef float gvec __attribute__((ext_vector_type(2 * kNS)));
-    typedef float evec __attribute__((ext_vector_type(2 * kPE)));
+    typedef float avec __attribute__((ext_vector_type(2 * kAG)));
+    typedef float evec __attribute__((ext_vector_type(2 * kNE)));
     hvec hq;
-    gvec gq;
+    avec aq, xq;  // ring addresses / X_SF of two groups of kAG steps (slot group % 2)
     evec eq;
-    auto sread = [&](uint32_t kb, uint32_t j, uint32_t slot) {  // stream entry j of block kb (j < 2 kDK)
-        const float* st = strm + ((w * 2 + ((kb + j / kDK) & 1u)) * kDK + j % kDK) * kDE;
-        const float4 h = *reinterpret_cast<const float4*>(st);
-        const float2 g = *reinterpret_cast<const float2*>(st + 4);
+    // entry j of block kb in the streams' two buffers (j < 2 kDK: the next block's past kDK - 1): the
+    // block's buffer or the other one (two bases per block, the rest is an immediate offset)
+    auto spos = [&](uint32_t kb, uint32_t j) {
+        const uint32_t e0 = (w * 2 + (kb & 1u)) * kDK;
+        return (j < kDK ? e0 : e0 ^ kDK) + j % kDK;
+    };
+    auto sread = [&](uint32_t kb, uint32_t j, uint32_t slot) {  // constants of step j
+        const float4 h = *reinterpret_cast<const float4*>(strm + spos(kb, j) * kDE);
         hq[4 * slot] = h.x;
         hq[4 * slot + 1] = h.y;
         hq[4 * slot + 2] = h.z;
         hq[4 * slot + 3] = h.w;
-        gq[2 * slot] = g.x;
-        gq[2 * slot + 1] = g.y;
     };
-    auto eread = [&](uint32_t sslot, uint32_t eslot) {
+    auto gread = [&](avec& q, const float* src, uint32_t kb, uint32_t j) {  // steps j .. j + kAG - 1 (kAG | j)
+        const float4 g = *reinterpret_cast<const float4*>(src + spos(kb, j));
+        const uint32_t slot = (j / kAG) % 2;
+        q[4 * slot] = g.x;
+        q[4 * slot + 1] = g.y;
+        q[4 * slot + 2] = g.z;
+        q[4 * slot + 3] = g.w;
+    };
+    auto eread = [&](uint32_t j) {  // ring pair of step j (< 2 kDK)
         // (the element copied to a scalar first: __builtin_bit_cast of an ext-vector element lvalue
         // reads the vector's first element)
-        const float roff = gq[2 * sslot + 1];
+        const float roff = aq[j % (2 * kAG)];
         const f2 e = lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u);
-        eq[2 * eslot] = e.x;
-        eq[2 * eslot + 1] = e.y;
+        eq[2 * (j % kNE)] = e.x;
+        eq[2 * (j % kNE) + 1] = e.y;
     };
 #pragma unroll
     for (uint32_t j = 0; j < kPS; ++j) sread(0, j, j);
+    gread(aq, adr, 0, 0);
+    gread(aq, adr, 0, kAG);
+    if (SX) gread(xq, xsf, 0, 0);
 #pragma unroll
-    for (uint32_t j = 0; j < kPE; ++j) eread(j, j);
+    for (uint32_t j = 0; j < kPE; ++j) eread(j);
 
     // the state as two register pairs: {F, c} (the feeder and the lane's sink partial: one packed add
     // advances both, {X_FF + F, X_SS + c}) and {x, -} (the lane's score: the source of the packed
     // heavy terms {A_F + x, A_S + x})
     f2 FC = (f2){F, c};
     f2 XP = (f2){xv, 0.0f};
-    auto step = [&](const float4& h, const float2& g2, const f2& e) {
+    auto step = [&](const float4& h, float xs, const f2& e) {
         const f2 Y = XP.xx + (f2){h.x, h.y};  // {A_F + x, A_S + x}
         const f2 Wv = FC + (f2){h.z, h.w};    // {F' = X_FF + F, X_SS + c}
         const float za = e.x + FC.x;          // ea + F
         const float zb = e.y + XP.x;          // eb + x
         float cn = fminf(Wv.y, Y.y);
-        if (SX) cn = fminf(cn, g2.x + FC.x);  // X_SF + F
-        push_lt(viol, Y.x, Wv.x);             // the speculation check: F' would have taken A_F + x
+        if (SX) cn = fminf(cn, xs + FC.x);    // X_SF + F
+        check_off(Y.x, Wv.x);                 // the speculation check: F' would have taken A_F + x
         XP.x = fminf(zb, za);
         FC = (f2){Wv.x, cn};
     };
@@ -297,31 +338,55 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         symload(kb + 2);
     };
     auto block = [&](uint32_t kb) {
+        __builtin_amdgcn_sched_barrier(0);  // the block's work stays above the first check
 #pragma unroll
         for (uint32_t j = 0; j < kDK; ++j) {
-            const uint32_t a = SVH_DIAG_AB == 1 ? 0u : j % kNS, b2 = j % kPE;
+            const uint32_t a = SVH_DIAG_AB == 1 ? 0u : j % kNS, b2 = j % kNE;
             const float4 h = make_float4(hq[4 * a], hq[4 * a + 1], hq[4 * a + 2], hq[4 * a + 3]);
-            const float2 g2 = make_float2(gq[2 * a], gq[2 * a + 1]);
+            const float xs = SX ? xq[SVH_DIAG_AB == 1 ? 0u : j % (2 * kAG)] : 0.0f;
             const f2 e = (f2){eq[2 * b2], eq[2 * b2 + 1]};
-            if (SVH_DIAG_AB != 2) eread((j + kPE) % kNS, j % kPE);  // ring pair of step j + kPE
-            // stream entries of steps j + kPS and j + kPS + 1 (the next block's past 31), read together
-            // at even steps (the two address words go out as one ds_read2_b32)
-            if (SVH_DIAG_AB != 1 && j % 2 == 0) {
-                sread(kb, j + kPS, (j + kPS) % kNS);
-                sread(kb, j + kPS + 1, (j + kPS + 1) % kNS);
+            // at even steps, together: the constants of steps j + kPS and j + kPS + 1 (the next block's
+            // past kDK - 1), then the ring pairs of steps j + kPE and j + kPE + 1, then, every kAG
+            // steps, the ring addresses of steps j + 2 kAG .. (into the slot of the group whose last
+            // pairs were just issued) and the X_SF of steps j + kAG ...  Whatever a read needs is
+            // older than the pairs the steps last waited for, so the only wait of two steps is the
+            // one for this step's and the next's pairs, with the reads issued since left in flight
+            // (four here and one group read, this step's or the one two steps back).  The compiler
+            // places its own counted waits where this one does not suffice: the count is a matter
+            // of speed only.
+            if (j % 2 == 0) {
+                if (SVH_DIAG_AB != 1) {
+                    sread(kb, j + kPS, (j + kPS) % kNS);
+                    sread(kb, j + kPS + 1, (j + kPS + 1) % kNS);
+                }
+                if (SVH_DIAG_AB != 2) {
+                    eread(j + kPE);
+                    eread(j + kPE + 1);
+                }
+                if (SVH_DIAG_AB != 1 && j % kAG == 0) {
+                    gread(aq, adr, kb, j + 2 * kAG);
+                    if (SX) gread(xq, xsf, kb, j + kAG);
+                }
+                if (SVH_DIAG_AB == 0) {
+                    __builtin_amdgcn_s_waitcnt(0xC07F | ((SX ? 6 : 5) << 8));  // lgkmcnt(5 or 6) alone
+                    __builtin_amdgcn_sched_barrier(0);                         // ahead of both steps' uses
+                }
             }
-            step(h, g2, e);
+            step(h, xs, e);
             if (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // keep the reads where they are issued
         }
+        exec_collect(alive);
     };
     // the row's last, partial block: plain steps
     auto tail = [&](uint32_t kb, uint32_t rem) {
-        const float* st = strm + (w * 2 + (kb & 1u)) * kDK * kDE;
+        const uint32_t e0 = (w * 2 + (kb & 1u)) * kDK;
+        __builtin_amdgcn_sched_barrier(0);
         for (uint32_t j = 0; j < rem; ++j) {
-            const float4 h = *reinterpret_cast<const float4*>(st + j * kDE);
-            const float2 g2 = *reinterpret_cast<const float2*>(st + j * kDE + 4);
-            step(h, g2, lds_ld2(__builtin_bit_cast(uint32_t, g2.y) + lane * 8u));
+            const float4 h = *reinterpret_cast<const float4*>(strm + (e0 + j) * kDE);
+            const float roff = adr[e0 + j];
+            step(h, SX ? xsf[e0 + j] : 0.0f, lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u));
         }
+        exec_collect(alive);  // right behind the loop's scalar branch: no other branch sees a partial EXEC
     };
 
     for (uint32_t k = 0; k < nbmax; ++k) {
@@ -364,7 +429,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         }
         wave_lexmin63(bv, bk);
         const float cmin = wave_min63(c);
-        const bool any_viol = __builtin_amdgcn_ballot_w64(viol != 0) != 0;
+        const bool any_viol = alive != ~0ull;
         if (lane == 63) {
             uint64_t* part = x.part + ((size_t)q * x.G + rg) * 2;
             part[0] = ((uint64_t)(any_viol ? 1u : 0u) << 32) | __builtin_bit_cast(uint32_t, cmin);
@@ -388,7 +453,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         }
         wave_lexmin63(bv, bk);
         const float cmin = wave_min63(c);
-        const bool any_viol = __builtin_amdgcn_ballot_w64(viol != 0) != 0;
+        const bool any_viol = alive != ~0ull;
         if (lane == 63) {
             uint64_t* part = x.part + ((size_t)q * x.G + rg) * 2;
             g_st64(part, ((uint64_t)(any_viol ? 1u : 0u) << 32) | __builtin_bit_cast(uint32_t, cmin));
@@ -496,11 +561,14 @@ const void* diag_ptr(bool sx) {
 
 uint32_t diag_waves_for(uint64_t nseq) { return nseq >= 4 ? 4u : nseq >= 2 ? 2u : 1u; }
 
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P) {
+static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx) {
     const size_t rerun = (2 * (size_t)P + 2 * W) * 4;  // pipe_rerun_row: v[2][P], red[2][W]
-    const size_t mainb = diag_lds_main(W, S);
+    const size_t mainb = diag_lds_main(W, S, sx);
     return mainb > rerun ? mainb : rerun;
 }
+
+// (the larger of the two kernels': models that use X_SF keep one stream more)
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P) { return diag_lds(W, S, P, true); }
 
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream) {
     if (!m.dtab || m.nrng == 0 || m.SM != 2 || m.S == 0 || m.S > kDMaxSym || (size_t)m.nrng * 64 > m.P || m.wide ||
@@ -509,7 +577,7 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     if (b.nseq == 0) return hipSuccess;
     const uint32_t W = diag_waves_for(b.nseq);
     const void* fn = W == 4 ? diag_ptr<4>(m.sx != 0) : W == 2 ? diag_ptr<2>(m.sx != 0) : diag_ptr<1>(m.sx != 0);
-    size_t lds = diag_lds_bytes(W, m.S, m.P);
+    size_t lds = diag_lds(W, m.S, m.P, m.sx != 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * m.nrng;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
