@@ -25,7 +25,7 @@ OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 
 CPP_TESTS := tests/cpp/test_HIP_impl tests/cpp/test_HIP_spec_impl tests/cpp/test_semantic_equality \
-             tests/cpp/test_readers_asan tests/cpp/test_host_asan
+             tests/cpp/test_readers_asan tests/cpp/test_host_asan tests/cpp/test_diag_sizes_asan
 
 .PHONY: all lib oracle ref tests tools clean
 all: lib oracle tests tools ref
@@ -87,6 +87,11 @@ $(BUILD)/asan/test_host_asan.o: tests/cpp/test_host_asan.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -c $< -o $@
 tests/cpp/test_host_asan: $(BUILD)/asan/test_host_asan.o $(ASAN_OBJS) $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS))
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN_HOST) -o $@ $^
+
+# The diagonal path variant's record sizes and offsets (kernels.h) under the same sanitizers: one
+# host-only program, no kernel objects.
+tests/cpp/test_diag_sizes_asan: tests/cpp/test_diag_sizes_asan.cpp $(CSRC)/kernels.h
+	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -o $@ $<
 
 # The reference benchmark harness's per-sequence call loop over HIP_impl / HIP_spec_impl.
 tools/bench_harness: tools/bench_harness.cpp $(LIB) include/HIP_impl.h include/HIP_spec_impl.h

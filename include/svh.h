@@ -93,9 +93,16 @@ enum { SVH_KERNEL_AUTO = 0, SVH_KERNEL_FUSED = 1, SVH_KERNEL_GENERIC = 2, SVH_KE
  * MSV-shaped models whose scores are all >= 0.
  * DIAG: the pipelined plan's recurrence with every lane on an anti-diagonal of the (state,
  * observation) grid: a state's chain input is the lane's own previous score, so no wave waits for
- * another (diag.hip).  Scores-only passes from the first observation; AUTO uses it for the batches
- * the latency plan used to take (svh_model_info.diag_max_nseq); selecting it runs every scores-only
- * pass of the model on it (decoded paths and the _spec tail use the chain kernel). */
+ * another (diag.hip).  AUTO uses it for the scores-only batches the latency plan used to take
+ * (svh_model_info.diag_max_nseq), rows resumed at a later observation and the _spec tail included;
+ * selecting it runs every scores-only pass of the model on it, and its decoded-path passes too
+ * where the model qualifies (svh_model_info.paths_kernel == SVH_KERNEL_DIAG: the feeder row wins
+ * every tie and feeds no term to the sink row, at most 2560 light states and 32 symbols, and the path variant's LDS leaves room for
+ * two workgroups per CU): the step then records a decision bit per cell, checkpoints and the
+ * per-observation light minima, and a traceback kernel walks them (pipe_paths.hip); rows whose
+ * speculation fails run on the chain kernel's path variant (svh_batch_fallbacks).  Other models
+ * decode their paths on the chain kernel, and svh_batch_plan says so.  AUTO's path batches keep
+ * the pipelined plan. */
 
 typedef struct {
     int32_t device;      /* HIP device ordinal; -1 = the caller's current device */

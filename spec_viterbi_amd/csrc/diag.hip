@@ -44,6 +44,8 @@
 // The last wave of a sequence to finish combines the ranges' partials (S, argmin, violation); a
 // row whose check failed is re-run exactly by that wave's workgroup (pipe_rerun_row) in the same
 // launch.
+// Decoded paths of models created with SVH_KERNEL_DIAG run the PATHS instantiations of the same
+// kernel (below; the record layouts are in kernels.h, the walk in pipe_paths.hip).
 #include "pipe_kernel.h"
 
 #include <cstdlib>
@@ -89,6 +91,13 @@ constexpr uint32_t kDMaxSym = 32;
 #ifndef SVH_DIAG_FINISH
 #define SVH_DIAG_FINISH 0
 #endif
+// SVH_DIAG_PAB (diagnostic builds of the path variant, timing only, wrong paths): 1 = no decision
+// bits, 2 = no ring writes and no folds (the light minima), 3 = no record stores at the blocks' ends
+// (words, checkpoints, F and sink checkpoints), 4 = one exec_collect and one fold per block (the ring
+// writes stay: against 2, the cost of the collects every 8 steps)
+#ifndef SVH_DIAG_PAB
+#define SVH_DIAG_PAB 0
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif
@@ -129,7 +138,23 @@ __host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool 
     return ((size_t)S * kDRS * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
 }
 
-template <int W, bool SX>
+// Decoded paths (PATHS; the walk is pipe_paths.hip's diag entry): fold ring [W][kFS][64] floats behind
+// the scores variant's LDS, 16-byte aligned.
+constexpr uint32_t kFS = 8;  // steps between two folds of a wave's scores into mu partials
+static_assert(kDK % kFS == 0 && 32 % kFS == 0 && kFS * 8 == 64, "fold: lane l reduces 8 lanes of step l / 8");
+__host__ __device__ constexpr size_t diag_lds_paths(uint32_t W, uint32_t S, bool sx) {
+    return ((diag_lds_main(W, S, sx) + 15) & ~(size_t)15) + (size_t)W * kFS * 64 * 4;
+}
+
+// PATHS: the step also records what the path walk reads (kernels.h, "Diagonal plan, decoded paths"):
+// a decision bit per step, shifted into a word per lane (one compare, one add with carry), the
+// lane's score into the wave's fold ring (one ds_write_b32); every kFS steps the wave folds the ring
+// into the range's light minima; every 32 observations it keeps the lane's score and {F, c} for the
+// block's end, where the words, the checkpoints and the range's sink partial are stored.  All of that
+// all-lanes work follows an exec_collect() of its own (one per kFS steps): no lane is off in it.
+// Begin is 0 for every row; a row whose check failed is not re-run here (its path needs the chain
+// kernel's records: the host's fallback launch takes it, x.viol).
+template <int W, bool SX, bool PATHS = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -248,6 +273,26 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     sbuild(0);
     symload(1);
 
+    // ---- decoded paths: this wave's record rows (lane-wise parts computed here, with every lane on)
+    const uint32_t Lg = rg * 64 + lane;                   // the lane's diagonal: position (Lg + t) mod NP at observation t
+    const uint32_t nck = len ? (len - 1) / kDiagCkptEvery + 1 : 0u;
+    uint32_t* dmq = nullptr;                              // [word][NP] + Lg
+    float *ckq = nullptr, *fckq = nullptr, *cckq = nullptr, *pmq = nullptr, *fr_wr = nullptr;
+    const float* fr_rd = nullptr;
+    uint32_t pcur = Lg;                                   // the lane's position at the last stored checkpoint
+    if constexpr (PATHS) {
+        float* fring = lds + ((diag_lds_main(W, S, SX) + 15) & ~(size_t)15) / 4 + w * kFS * 64;
+        fr_wr = fring + lane;                             // step s of a fold group: + 64 s
+        fr_rd = fring + lane * 8;                         // step lane / 8, lanes 8 (lane % 8) .. + 7
+        if (real) {
+            dmq = b.cmask + b.cmask_off[q] + Lg;
+            ckq = b.ckpt + b.ckpt_off[q];
+            fckq = b.fck + b.fck_off[q];
+            cckq = reinterpret_cast<float*>(b.hrec + b.hrec_off[q]) + (size_t)rg * nck;
+            pmq = reinterpret_cast<float*>(b.prec) + b.prec_off[q] + (size_t)rg * len + (lane >> 3);
+        }
+    }
+
     // ---- state at observation first - 1
     float xv = kInf, F = kInf, c = kInf;
     uint64_t alive = ~0ull;  // lanes whose check has held so far (collected from EXEC after every block)
@@ -263,6 +308,18 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         xv = r != kNoRow ? vin[r] : kInf;
         F = m.rowF >= 0 ? vin[m.rowF] : kInf;
         c = (rg == 0 && lane == 0 && m.rowS >= 0) ? vin[m.rowS] : kInf;
+    }
+    if constexpr (PATHS) {  // the records of observation 0
+        if (real) {
+            ckq[Lg] = xv;
+            float mu0 = xv, c0 = c;
+            wave_min63x2(mu0, c0);
+            if (lane == 63) {
+                pmq[-7] = mu0;  // (lane 63: pmq is the range's row + 7)
+                cckq[0] = c0;
+            }
+            if (rg == 0 && lane == 0) fckq[0] = F;
+        }
     }
     __syncthreads();  // ring groups 0..3, wnb
     uint32_t nbmax = 0;
@@ -320,7 +377,8 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     // heavy terms {A_F + x, A_S + x})
     f2 FC = (f2){F, c};
     f2 XP = (f2){xv, 0.0f};
-    auto step = [&](const float4& h, float xs, const f2& e) {
+    uint32_t dw = 0;  // PATHS: the decision bits of the last 32 steps, the latest in bit 0
+    auto step = [&](const float4& h, float xs, const f2& e, uint32_t slot = 0) {
         const f2 Y = XP.xx + (f2){h.x, h.y};  // {A_F + x, A_S + x}
         const f2 Wv = FC + (f2){h.z, h.w};    // {F' = X_FF + F, X_SS + c}
         const float za = e.x + FC.x;          // ea + F
@@ -328,8 +386,88 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         float cn = fminf(Wv.y, Y.y);
         if (SX) cn = fminf(cn, xs + FC.x);    // X_SF + F
         check_off(Y.x, Wv.x);                 // the speculation check: F' would have taken A_F + x
+        if constexpr (PATHS && SVH_DIAG_PAB != 1) push_le(dw, za, zb);  // F's term taken (F wins every tie: ties_heavy)
         XP.x = fminf(zb, za);
         FC = (f2){Wv.x, cn};
+        if constexpr (PATHS && SVH_DIAG_PAB != 2) fr_wr[slot * 64] = XP.x;
+    };
+    // PATHS, after an exec_collect: the last n <= kFS steps' scores (observations t0 .. t0 + n - 1) ->
+    // the range's light minima.  Lane l takes lanes 8 (l % 8) .. + 7 of step l / 8; three DPP stages
+    // join the step's 8 lanes.  In two halves: fold_read issues the lane's two ring reads, fold_min
+    // reduces and stores them -- in a full block one collect later, so that the reads' latency passes
+    // under the next 8 steps (the ring's slots may be rewritten meanwhile: LDS operations of a wave
+    // execute in order).  The record's index and the values read go through registers defined behind
+    // the collect, so that nothing lane-wise of the fold can be computed while lanes are off.
+    float4 fa0 = make_float4(kInf, kInf, kInf, kInf), fa1 = fa0;
+    auto fold_read = [&]() {
+        if (SVH_DIAG_PAB == 2) return;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        fa0 = *reinterpret_cast<const float4*>(fr_rd);
+        fa1 = *reinterpret_cast<const float4*>(fr_rd + 4);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+    auto fold_min = [&](uint32_t t0, uint32_t n) {
+        if (SVH_DIAG_PAB == 2) return;
+        uint32_t tv = t0;
+        float4 a0 = fa0, a1 = fa1;
+        asm volatile("" : "+v"(tv), "+v"(a0.x), "+v"(a0.y), "+v"(a0.z), "+v"(a0.w), "+v"(a1.x), "+v"(a1.y), "+v"(a1.z), "+v"(a1.w));
+        float mn = fminf(fminf(fminf(a0.x, a0.y), fminf(a0.z, a0.w)), fminf(fminf(a1.x, a1.y), fminf(a1.z, a1.w)));
+        const uint32_t inf = 0x7f800000u;
+        mn = fminf(mn, __builtin_bit_cast(float, dpp_u<0xB1>(__builtin_bit_cast(uint32_t, mn), inf)));   // quad_perm [1,0,3,2]
+        mn = fminf(mn, __builtin_bit_cast(float, dpp_u<0x4E>(__builtin_bit_cast(uint32_t, mn), inf)));   // quad_perm [2,3,0,1]
+        mn = fminf(mn, __builtin_bit_cast(float, dpp_u<0x141>(__builtin_bit_cast(uint32_t, mn), inf)));  // row_half_mirror
+        if ((lane & 7u) == 0 && (lane >> 3) < n) pmq[tv] = mn;  // (pmq: the range's row + lane / 8)
+    };
+    auto fold = [&](uint32_t t0, uint32_t n) {
+        fold_read();
+        fold_min(t0, n);
+    };
+    // PATHS: what a block keeps of its 32nd step and stores at its end
+    uint32_t dw0 = 0;
+    float xs0 = kInf, fs0 = kInf, cs0 = kInf;
+    auto keep32 = [&]() {
+        dw0 = dw;
+        xs0 = XP.x;
+        fs0 = FC.x;
+        cs0 = FC.y;
+    };
+    // PATHS, after the block's last exec_collect: the records of block kb, rem of its steps run
+    // (rem = kDK: dw0 / dw hold rows 64 kb .. + 31 / + 32 .. + 63; a partial word is left-aligned: row r
+    // is bit 31 - r % 32); checkpoints of observations 64 kb + 32 (kept) and 64 kb + 64 (the state)
+    auto block_records = [&](uint32_t kb, uint32_t rem) {
+        if (SVH_DIAG_PAB == 3) {  // (the kept values stay live)
+            asm volatile("" : : "v"(dw0), "v"(dw), "v"(xs0), "v"(fs0), "v"(cs0));
+            return;
+        }
+        // (as in fold: what the stores' addresses and the DPP reduction are made of is defined here,
+        // behind the collect)
+        uint32_t kv = kb, pc = pcur;
+        float cn1 = cs0, cn2 = FC.y;
+        asm volatile("" : "+v"(kv), "+v"(pc), "+v"(cn1), "+v"(cn2));
+        const uint32_t w0 = rem > 32 ? dw0 : dw << (32u - rem);
+        dmq[(size_t)(2 * kv) * NP] = w0;
+        if (rem > 32) dmq[(size_t)(2 * kv + 1) * NP] = dw << (64u - rem);
+        if (rem >= 32) {
+            const bool two = rem == 64;
+            uint32_t p1 = pc + 32;
+            p1 = p1 >= NP ? p1 - NP : p1;
+            uint32_t p2 = p1 + 32;
+            p2 = p2 >= NP ? p2 - NP : p2;
+            const float x1 = rem > 32 ? xs0 : XP.x, f1 = rem > 32 ? fs0 : FC.x;
+            float c1 = rem > 32 ? cn1 : cn2, c2 = cn2;
+            ckq[(size_t)(2 * kv + 1) * NP + p1] = x1;
+            if (two) ckq[(size_t)(2 * kv + 2) * NP + p2] = XP.x;
+            wave_min63x2(c1, c2);
+            if (lane == 63) {
+                cckq[2 * kv + 1] = c1;
+                if (two) cckq[2 * kv + 2] = c2;
+            }
+            if (rg == 0 && lane == 0) {
+                fckq[2 * kv + 1] = f1;
+                if (two) fckq[2 * kv + 2] = FC.x;
+            }
+            pcur = p2;
+        }
     };
     auto blockwork = [&](uint32_t kb) {
         lwrite(kb + 4);  // into the slots of group kb - 1, which no wave reads any more
@@ -368,18 +506,50 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
                     if (SX) gread(xq, xsf, kb, j + kAG);
                 }
                 if (SVH_DIAG_AB == 0) {
-                    __builtin_amdgcn_s_waitcnt(0xC07F | ((SX ? 6 : 5) << 8));  // lgkmcnt(5 or 6) alone
+                    // lgkmcnt(5 or 6) alone (PATHS: and the two ring writes since the pairs' reads)
+                    __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0)) << 8));
                     __builtin_amdgcn_sched_barrier(0);                         // ahead of both steps' uses
                 }
             }
-            step(h, xs, e);
+            step(h, xs, e, j % kFS);
             if (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // keep the reads where they are issued
+            if constexpr (PATHS) {
+                if (j % kFS == kFS - 1 && (SVH_DIAG_PAB != 4 || j == kDK - 1)) {
+                    exec_collect(alive);
+                    if (SVH_DIAG_PAB == 4) {
+                        fold(kb * kDK + 1 + j - (kFS - 1), kFS);
+                    } else {  // the group before this one, then this one's reads; the block's last at once
+                        if (j >= kFS) fold_min(kb * kDK + 1 + j - (2 * kFS - 1), kFS);
+                        fold_read();
+                        if (j == kDK - 1) fold_min(kb * kDK + 1 + j - (kFS - 1), kFS);
+                    }
+                    if (j == 31) keep32();
+                    if (j == kDK - 1) block_records(kb, kDK);
+                    __builtin_amdgcn_sched_barrier(0);  // the next steps' first check stays below
+                }
+            }
         }
-        exec_collect(alive);
+        if constexpr (!PATHS) exec_collect(alive);
     };
     // the row's last, partial block: plain steps
     auto tail = [&](uint32_t kb, uint32_t rem) {
         const uint32_t e0 = (w * 2 + (kb & 1u)) * kDK;
+        if constexpr (PATHS) {  // groups of kFS steps, each with its collect and fold
+            for (uint32_t g0 = 0; g0 < rem; g0 += kFS) {
+                const uint32_t n = rem - g0 < kFS ? rem - g0 : kFS;
+                __builtin_amdgcn_sched_barrier(0);
+                for (uint32_t j = g0; j < g0 + n; ++j) {
+                    const float4 h = *reinterpret_cast<const float4*>(strm + (e0 + j) * kDE);
+                    const float roff = adr[e0 + j];
+                    step(h, SX ? xsf[e0 + j] : 0.0f, lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u), j - g0);
+                }
+                exec_collect(alive);
+                fold(kb * kDK + 1 + g0, n);
+                if (g0 + n == 32 && rem > 32) keep32();
+            }
+            block_records(kb, rem);
+            return;
+        }
         __builtin_amdgcn_sched_barrier(0);
         for (uint32_t j = 0; j < rem; ++j) {
             const float4 h = *reinterpret_cast<const float4*>(strm + (e0 + j) * kDE);
@@ -497,11 +667,12 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             if (b.best) b.best[q] = bk2 == kNoRow ? -1 : (int64_t)bk2;
             x.viol[q] = any ? 1u : 0u;
             __hip_atomic_store(x.done + (size_t)q * SVH_DIAG_DONE_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (any) rrow[w] = q;
+            if (any && !PATHS) rrow[w] = q;
         }
     }
     // rows whose speculation failed: re-run exactly by this workgroup (pipe_rerun_row, the latency
     // plan's serial recurrence with F's light term restored) -- no second launch on the common path
+    if constexpr (PATHS) return;  // (the host's chain fallback re-runs them with their path records)
     __syncthreads();
     uint32_t rq[W];  // read before any re-run: its scores overwrite this part of the LDS
 #pragma unroll
@@ -556,6 +727,15 @@ const void* diag_ptr(bool sx) {
     return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true>)
               : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false>);
 }
+// (Only the instantiations without X_SF: with both PATHS and SX the block's body is past the
+// compiler's limit for `#pragma unroll`, the 64 steps are then unrolled in part, the register
+// vectors indexed at run time, and the kernel is some 600 instructions per step.  Models whose S
+// takes a term from F keep the chain path variant: diag_paths_fit.)
+template <int W>
+const void* diag_paths_ptr() {
+    static_assert(kDK == 64, "the path records' block layout (two mask words, two checkpoints per block)");
+    return reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, true>);
+}
 
 }  // namespace
 
@@ -570,14 +750,31 @@ static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx) {
 // (the larger of the two kernels': models that use X_SF keep one stream more)
 size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P) { return diag_lds(W, S, P, true); }
 
+size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx) { return diag_lds_paths(W, S, sx); }
+
+// The path variant keeps two workgroups on a CU at every width (the headline's 494 workgroups need
+// them on 256 CUs): a model whose LDS does not allow that is not planned on it; nor is one whose S
+// takes a term from F (sx: no such instantiation, see diag_paths_ptr).
+bool diag_paths_fit(uint32_t S, bool sx) {
+    return !sx && SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0 && kDK == 64 && S > 0 && S <= kDMaxSym &&
+           diag_lds_paths(4, S, sx) <= kDiagPathsLdsMax;
+}
+
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream) {
+    const bool paths = b.cmask != nullptr;
     if (!m.dtab || m.nrng == 0 || m.SM != 2 || m.S == 0 || m.S > kDMaxSym || (size_t)m.nrng * 64 > m.P || m.wide ||
-        b.cmask || b.run_mask || (b.v_in && !b.v_in_row) || !x.part || !x.done || !x.viol || b.nseq > x.rows || x.G < m.nrng)
+        b.run_mask || (b.v_in && !b.v_in_row) || !x.part || !x.done || !x.viol || b.nseq > x.rows || x.G < m.nrng)
+        return hipErrorInvalidValue;
+    // decoded paths: every record buffer, every row from observation 0, F winning every tie (one
+    // compare per decision bit), two workgroups per CU
+    if (paths && (!b.cmask_off || !b.ckpt || !b.ckpt_off || !b.fck || !b.fck_off || !b.hrec || !b.hrec_off || !b.prec ||
+                  !b.prec_off || b.v_in || !m.ties_heavy || !diag_paths_fit(m.S, m.sx != 0)))
         return hipErrorInvalidValue;
     if (b.nseq == 0) return hipSuccess;
     const uint32_t W = diag_waves_for(b.nseq);
-    const void* fn = W == 4 ? diag_ptr<4>(m.sx != 0) : W == 2 ? diag_ptr<2>(m.sx != 0) : diag_ptr<1>(m.sx != 0);
-    size_t lds = diag_lds(W, m.S, m.P, m.sx != 0);
+    const void* fn = paths ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
+                           : (W == 4 ? diag_ptr<4>(m.sx != 0) : W == 2 ? diag_ptr<2>(m.sx != 0) : diag_ptr<1>(m.sx != 0));
+    size_t lds = paths ? diag_lds_paths(W, m.S, m.sx != 0) : diag_lds(W, m.S, m.P, m.sx != 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * m.nrng;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;

@@ -306,10 +306,40 @@ inline size_t pipe_path_lds_bytes(uint32_t W) { return (size_t)W * 8 * kPQuadStr
 // (position, observation) grid -- lane l of range r holds position (64 r + l + i) mod (64 nrng) after
 // step i, so a position's chain input is the lane's own previous score (no exchange between waves).
 // A workgroup is diag_waves_for(nseq) sequences x one range; rows whose speculation fails are re-run
-// in the same launch.  Scores only; a row starts at observation 0 or resumes at begin > 0 from v_in.
+// in the same launch.  A scores row starts at observation 0 or resumes at begin > 0 from v_in.
 uint32_t diag_waves_for(uint64_t nseq);
 size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P);
+// b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
+// Diagonal plan, decoded paths (diag.hip PATHS, pipe_paths.hip's diag walk).  Models whose F wins
+// every tie (PipeModel::ties_heavy) and whose S takes no term from F (sx == 0).  Rows whose speculation fails are flagged in x.viol and left to
+// the chain kernel's path variant, as on the pipelined plan.  Per sequence of length len, with
+// NP = 64 nrng diagonals (diagonal L holds position (L + t) mod NP at observation t) and the
+// FusedBatch fields that carry them:
+//   cmask: decision words [ceil((len - 1) / 32)][NP], diagonal-major: bit 31 - r % 32 of word
+//          [r / 32][L] says that position (L + r + 1) mod NP took F's term at observation r + 1 (a
+//          light run of the walk stays on one diagonal: one L, consecutive bits)
+//   ckpt:  the light scores of every kDiagCkptEvery-th observation, [t / kDiagCkptEvery][NP] by position
+//   fck:   F(32 k), as on the pipelined plan
+//   prec:  viewed as float [nrng][len]: the minimum of range u's 64 scores at observation t
+//          (mu(t) = min over u, exact)
+//   hrec:  viewed as float [nrng][(len - 1) / 32 + 1]: the minimum of range u's sink partials at
+//          observation 32 k (C(32 k) = min over u); the walk rebuilds S's score between two
+//          checkpoints from mu:  C(t) = min(fl(X_SS(o_t) + C(t-1)), fl(A_S(o_t) + mu(t-1))), bit for
+//          bit the recurrence's own value: fl(A_S + .) is monotone, so min_p fl(A_S + v_p) =
+//          fl(A_S + min_p v_p)
+constexpr uint32_t kDiagCkptEvery = 32;
+constexpr size_t kDiagPathsLdsMax = 80 * 1024;  // two workgroups per CU
+inline uint64_t diag_mask_words(uint64_t len, uint32_t nrng) { return len > 1 ? (len - 1 + 31) / 32 * (uint64_t)nrng * 64 : 0; }
+inline uint64_t diag_ckpt_floats(uint64_t len, uint32_t nrng) {
+    return len ? ((len - 1) / kDiagCkptEvery + 1) * (uint64_t)nrng * 64 : 0;
+}
+inline uint64_t diag_mu_floats(uint64_t len, uint32_t nrng) { return (uint64_t)nrng * len; }
+inline uint64_t diag_cck_floats(uint64_t len, uint32_t nrng) { return len ? ((len - 1) / 32 + 1) * (uint64_t)nrng : 0; }
+size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx);
+bool diag_paths_fit(uint32_t S, bool sx);  // S takes no term from F, and the LDS allows two workgroups per CU
+hipError_t launch_diag_traceback(const PipeModel& m, const FusedBatch& b, const uint64_t* path_off, int32_t* paths,
+                                 const uint32_t* skip, hipStream_t stream);
 
 // Wide pipelined plan (pipe_wide.hip): one block of 64*SM positions per workgroup, W sequences
 // (one per wave), the block's table [nblk][S][NC][64] float4 in LDS (PipeModel.tab; G = nblk);

@@ -17,6 +17,8 @@
 // with fl(cA + v[j]) == fl(cA + mu) is recomputed from the light checkpoint below that row.
 #include "pipe_common.h"
 
+#include <type_traits>
+
 namespace svh {
 
 using namespace dev;
@@ -78,6 +80,74 @@ struct RecSrc {
     __device__ float C(uint32_t r) const { return r ? reduce(r, 1) : c0; }
 };
 
+// The same inputs from the diagonal plan's records (kernels.h, "Diagonal plan, decoded paths"): mu(r)
+// from the ranges' minima [u][r]; F as above; S's score C is not recorded per observation: the walk
+// rebuilds a round's values from the checkpoint below them (DiagCWin).
+struct DiagSrc {
+    const float* pmu;
+    const float* fck;
+    const uint8_t* sym;
+    const float* hcl;
+    uint32_t len, U;
+    __device__ float F(uint32_t r) const {
+        RecSrc f;
+        f.fck = fck;
+        f.sym = sym;
+        f.hcl = hcl;
+        return f.F(r);
+    }
+    __device__ float mu(uint32_t r) const {
+        float acc = kInf;
+        uint32_t u = 0;
+        for (; u + 8 <= U; u += 8) {
+            float x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = pmu[(size_t)(u + k) * len + r];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc = fminf(acc, x[k]);
+        }
+        for (; u < U; ++u) acc = fminf(acc, pmu[(size_t)u * len + r]);
+        return acc;
+    }
+};
+
+// S's scores of a round of the walk, diagonal plan: lane l's C(i - 1 - l) for the round's records
+// (i >= 1), rebuilt serially from the checkpoint C(base), base = the round's lowest record rounded
+// down to 32 (at most 94 steps):
+//     C(t) = min( fl(X_SS(o_t) + C(t-1)), fl(A_S(o_t) + mu(t-1)) )
+// -- the recurrence's own operations (kernels.h gives the argument; no term from F: models whose S
+// has one are not planned on the diagonal path variant, diag_paths_fit).  The lanes first stage every
+// step's two operands in LDS (cw: 2 x 96 floats), then all run the same chain.
+constexpr uint32_t kDiagCWin = 96;
+__device__ float diag_c_window(const PipeModel& m, const DiagSrc& ds, const float* cck, uint32_t nck, float c0, int64_t i,
+                               float* cw) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t hi = (uint32_t)(i - 1), lo = i > 64 ? (uint32_t)(i - 64) : 0u, base = lo & ~31u;
+    float cb = kInf;
+    if (base == 0) {
+        cb = c0;
+    } else {
+        for (uint32_t u = lane; u < ds.U; u += 64) cb = fminf(cb, cck[(size_t)u * nck + (base >> 5)]);
+        for (int off = 32; off >= 1; off >>= 1) cb = fminf(cb, __shfl_xor(cb, off));
+    }
+    const uint32_t n = hi - base;  // steps base + 1 .. hi
+    for (uint32_t k = lane; k < n; k += 64) {
+        const uint32_t t = base + 1 + k;
+        const float* hc = ds.hcl + (size_t)ds.sym[t] * 8;  // A_S A_F X_SS X_FF X_SF
+        cw[k] = hc[0] + ds.mu(t - 1);
+        cw[kDiagCWin + k] = hc[2];
+    }
+    wave_sync();
+    const uint32_t mine = hi - lane;  // this lane's record (lanes past the round's records: unused)
+    float C = cb, out = cb;
+    for (uint32_t k = 0; k < n; ++k) {
+        C = fminf(cw[kDiagCWin + k] + C, cw[k]);
+        out = base + 1 + k == mine ? C : out;
+    }
+    wave_sync();  // cw is reused (the next round, pipe_jstar)
+    return out;
+}
+
 // (eb, ea) of position x for symbol o in the plan's table layout: the latency plan's
 // [nblk][S][SM][64] float2, or the wide plan's [nblk][S][NC][64] float4 chunks ([eb_1 .. eb_{SM-1},
 // eb_0] then [ea_0 .. ea_{SM-1}], pipe_wide_kernel.h).
@@ -94,13 +164,16 @@ __device__ __forceinline__ float2 pipe_tab_pair(const PipeModel& m, uint32_t x, 
 // observation r+1.  v_r is recomputed by one wave from the checkpoint row c = r rounded down to
 // kCkptEvery with the kernel's float operations: v_i[p] = fminf(fl(ea_p + F(i-1)),
 // fl(eb_p + v_{i-1}[p-1])) (v_{i-1}[-1] = +inf), F advanced alongside from F(c).
-__device__ uint32_t pipe_jstar(const PipeModel& m, const RecSrc& rs, const float* ck, uint32_t r, uint32_t h,
-                               float* buf) {
-    const uint32_t lane = threadIdx.x & 63u, P = m.P;
-    const uint32_t c = r / kCkptEvery * kCkptEvery;
+// (EVERY: the plan's checkpoint interval; P: the positions a checkpoint row holds -- the diagonal
+// plan's 64 nrng, every light position among them)
+template <uint32_t EVERY, class Src>
+__device__ uint32_t pipe_jstar(const PipeModel& m, const Src& rs, const float* ck, uint32_t r, uint32_t h, float* buf,
+                               uint32_t P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c = r / EVERY * EVERY;
     float* cur = buf;
     float* nxt = buf + kPTbMaxP;
-    const float* ckr = ck + (size_t)(c / kCkptEvery) * P;
+    const float* ckr = ck + (size_t)(c / EVERY) * P;
     for (uint32_t x = lane; x < P; x += 64) cur[x] = ckr[x];
     float F = rs.F(c);
     wave_sync();
@@ -133,6 +206,9 @@ __device__ uint32_t pipe_jstar(const PipeModel& m, const RecSrc& rs, const float
 // its row is below every light row, the kernel's exact speculation check (no light term of F ever
 // below its self term on a row this kernel traces) already decides F's backpointer: itself, with
 // no loads; S (and F otherwise) rebuild their inputs on demand (RecSrc).
+// DIAG: the diagonal plan's records (DiagSrc): the light run reads one diagonal's words, S's scores
+// of a round come from diag_c_window, j* from the plan's own checkpoint rows.
+template <bool DIAG>
 __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBatch b, const uint64_t* path_off,
                                                              int32_t* paths, const uint32_t* skip) {
     __shared__ float buf[2 * kPTbMaxP];
@@ -152,15 +228,23 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
     }
     const uint32_t len = b.end[q];
     const uint32_t nblk = m.nblk, SM = m.SM, bsz = 64 * SM;
-    RecSrc rs;
-    rs.prec = b.prec + b.prec_off[q];
+    typename std::conditional<DIAG, DiagSrc, RecSrc>::type rs;
+    if constexpr (DIAG) {
+        rs.pmu = reinterpret_cast<const float*>(b.prec) + b.prec_off[q];
+        rs.U = m.nrng;
+    } else {
+        rs.prec = b.prec + b.prec_off[q];
+        rs.U = pipe_prec_parts(m.wide != 0) * nblk;
+    }
     rs.fck = b.fck + b.fck_off[q];
     rs.sym = b.symbols + b.sym_off[q];
     rs.hcl = hcl;
     rs.len = len;
-    rs.U = pipe_prec_parts(m.wide != 0) * nblk;
     wave_sync();
-    rs.c0 = m.rowS >= 0 ? hcl[(size_t)rs.sym[0] * 8 + 6] + m.startS : kInf;
+    const float c0 = m.rowS >= 0 ? hcl[(size_t)rs.sym[0] * 8 + 6] + m.startS : kInf;
+    if constexpr (!DIAG) rs.c0 = c0;
+    const uint32_t NPd = m.nrng * 64, nck = len ? (len - 1) / 32 + 1 : 0u;                           // DIAG
+    const float* cck = DIAG ? reinterpret_cast<const float*>(b.hrec + b.hrec_off[q]) : nullptr;  // DIAG
     // F's backpointer is itself wherever the kernel's check held (see above)
     const bool f_self = ((m.hx_exist & 1u) != 0) && (!(m.hl_exist & 1u) || (uint32_t)m.rowF < lrowl[0]);
 
@@ -186,11 +270,18 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
         float hv = kInf, lv = kInf;
         uint32_t hcol = 0xFFFFFFFFu;
         bool hex = false;
+        float cl = kInf;  // DIAG: S's score of this lane's record
+        if constexpr (DIAG) {
+            if (pos == -2) cl = diag_c_window(m, rs, cck, nck, c0, i, buf);  // (pos is the wave's: no lane diverges)
+        }
         if (pos >= 0) {  // light run: lane l looks at position pos-l at observation i-l
             const int64_t p = (int64_t)pos - (int64_t)lane;
             if (valid && p >= 0) {
                 const uint32_t pp = (uint32_t)p, blk = pp / bsz, ln = (pp % bsz) / SM, ss = pp % SM;
-                const uint32_t word = msk[((uint64_t)r >> 5) * wstride + (blk * SM + ss) * 64 + ln];
+                // DIAG: every lane's cell is on the diagonal (pos - i) mod NP
+                const uint32_t dg = (uint32_t)(((int64_t)pos + NPd - i % NPd) % NPd);
+                const uint32_t word = DIAG ? msk[((uint64_t)r >> 5) * NPd + dg]
+                                           : msk[((uint64_t)r >> 5) * wstride + (blk * SM + ss) * 64 + ln];
                 const uint32_t f = pfl[pp];
                 if ((word >> (31u - ((uint32_t)r & 31u))) & 1u) {
                     pred = m.rowF;
@@ -214,7 +305,10 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
                 if ((m.hx_exist >> (h * 2 + k)) & 1u) {
                     // X[h][k]: F <- F = X_FF, S <- F = X_SF, S <- S = X_SS (F <- S never: plan)
                     const float cx = h == 0 ? hc[3] : (k == 0 ? hc[4] : hc[2]);
-                    const float val = cx + (k == 0 ? rs.F(rr) : rs.C(rr));
+                    float ck1;
+                    if constexpr (DIAG) ck1 = cl;  // (F <- S never: only S's own record asks)
+                    else ck1 = rs.C(rr);
+                    const float val = cx + (k == 0 ? rs.F(rr) : ck1);
                     const uint32_t col = (uint32_t)hrowk[k];
                     const bool take = !hex || val < hv || (val == hv && col < hcol);
                     hv = take ? val : hv;
@@ -233,7 +327,8 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
         uint32_t ls = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;  // first lane leaving the run
         while (ls < 64u && __builtin_amdgcn_readlane((int)needj, (int)ls)) {
             const uint32_t rj = (uint32_t)(i - 1 - (int64_t)ls);
-            const uint32_t jp = pipe_jstar(m, rs, ck, rj, (uint32_t)(-1 - pos), buf);
+            const uint32_t jp = DIAG ? pipe_jstar<kDiagCkptEvery>(m, rs, ck, rj, (uint32_t)(-1 - pos), buf, NPd)
+                                     : pipe_jstar<kCkptEvery>(m, rs, ck, rj, (uint32_t)(-1 - pos), buf, m.P);
             if (lane == ls) {
                 const uint32_t js = jp == 0xFFFFFFFFu ? 0xFFFFFFFFu : lrowl[jp];
                 const uint32_t k = !hex || lv < hv ? js : min(hcol, js);
@@ -260,7 +355,17 @@ hipError_t launch_pipe_traceback(const PipeModel& m, const FusedBatch& b, const 
         m.S > 32)
         return hipErrorInvalidValue;
     if (b.nseq == 0) return hipSuccess;
-    hipLaunchKernelGGL(pipe_traceback_kernel, dim3(b.nseq), dim3(64), 0, stream, m, b, path_off, paths, skip);
+    hipLaunchKernelGGL(pipe_traceback_kernel<false>, dim3(b.nseq), dim3(64), 0, stream, m, b, path_off, paths, skip);
+    return hipGetLastError();
+}
+
+hipError_t launch_diag_traceback(const PipeModel& m, const FusedBatch& b, const uint64_t* path_off, int32_t* paths,
+                                 const uint32_t* skip, hipStream_t stream) {
+    if (!b.cmask || !b.ckpt || !b.prec || !b.fck || !b.hrec || !m.tab || m.wide || !m.nrng || !m.ties_heavy || m.sx ||
+        !m.pflags || !m.spos || m.P > kPTbMaxP || (size_t)m.nrng * 64 > m.P || m.n > kPTbMaxN || m.S > 32)
+        return hipErrorInvalidValue;
+    if (b.nseq == 0) return hipSuccess;
+    hipLaunchKernelGGL(pipe_traceback_kernel<true>, dim3(b.nseq), dim3(64), 0, stream, m, b, path_off, paths, skip);
     return hipGetLastError();
 }
 

@@ -1208,6 +1208,16 @@ const DevicePipePlan* Model::pipe_paths_for(uint32_t nseq) const {
     return nullptr;
 }
 
+const DevicePipePlan* Model::diag_paths_for(uint32_t nseq) const {
+    (void)nseq;
+    if (kernel_pref != SVH_KERNEL_DIAG || !pipe.plan.ok || !pipe.view.dtab || !band.plan.paths_ok()) return nullptr;
+    const PipePlan& p = pipe.plan;
+    if (!p.ties_heavy || p.wide || p.P > kPipeTbMaxP || host.n > kPipeTbMaxP + 2 || host.S > 32 ||
+        (uint64_t)p.nrng * 64 > p.P || !diag_paths_fit(host.S, p.sx))
+        return nullptr;
+    return &pipe;
+}
+
 bool Model::pipe_l2_on() const {
     return spec2_on && pipe.plan.ok && pipe_l2_supported(pipe.view) &&
            (kernel_pref == SVH_KERNEL_AUTO || kernel_pref == SVH_KERNEL_PIPE);
@@ -1487,7 +1497,8 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
     i.spec_level = spec_level;
     i.spec_bytes = d_products.bytes;
     const DevicePipePlan* pp1 = pipe_paths_for(1);
-    i.paths_kernel = pp1 ? (pp1->plan.wide ? SVH_KERNEL_PIPE_WIDE : SVH_KERNEL_PIPE)
+    i.paths_kernel = diag_paths_for(1) ? SVH_KERNEL_DIAG
+                     : pp1 ? (pp1->plan.wide ? SVH_KERNEL_PIPE_WIDE : SVH_KERNEL_PIPE)
                      : band_for(true) ? SVH_KERNEL_CHAIN : plan_for(true) ? SVH_KERNEL_FUSED : SVH_KERNEL_GENERIC;
     i.wide_threads = band_wide.plan.ok && band_for(false) ? (int32_t)band_wide.plan.B : 0;
     i.wide_slots = band_wide.plan.ok && band_for(false) ? (int32_t)band_wide.plan.SM : 0;
@@ -1522,6 +1533,13 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
         i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P);
+    }
+    if (paths && steps && level <= 1 && nseq && diag_paths_for(nseq)) {  // decoded paths on the diagonal plan
+        const uint32_t w = diag_waves_for(nseq);
+        i.kernel = SVH_KERNEL_DIAG;
+        i.threads = (int32_t)(64 * w);
+        i.slots = 1;
+        i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);
     }
     if (pipe.view.dtab) {
         i.diag_ranges = (int32_t)pipe.plan.nrng;
@@ -1592,6 +1610,9 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     nseq = (uint32_t)nseq_;
     const DevicePipePlan* ppl = chain_paths ? model->pipe_paths_for(nseq) : nullptr;
     pipe_paths = ppl != nullptr;
+    const DevicePipePlan* dpl = chain_paths && !ppl ? model->diag_paths_for(nseq) : nullptr;
+    diag_paths = dpl != nullptr;
+    const bool recs = pipe_paths || diag_paths;  // the four record buffers of either plan
     offsets.assign(offs, offs + nseq + 1);
     lens.resize(nseq);
     h_symoff.resize(nseq);
@@ -1600,11 +1621,12 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     h_cmoff.resize(nseq);
     h_hroff.resize(nseq);
     h_ckoff.resize(nseq);
-    h_pmoff.resize(pipe_paths ? nseq : 0);
-    h_proff.resize(pipe_paths ? nseq : 0);
-    h_pcoff.resize(pipe_paths ? nseq : 0);
-    h_fcoff.resize(pipe_paths ? nseq : 0);
-    uint64_t bytes = 0, bpn = 0, cmn = 0, hrn = 0, ckn = 0, pmn = 0, prn = 0, pcn = 0, fcn = 0;
+    h_pmoff.resize(recs ? nseq : 0);
+    h_proff.resize(recs ? nseq : 0);
+    h_pcoff.resize(recs ? nseq : 0);
+    h_fcoff.resize(recs ? nseq : 0);
+    h_dcoff.resize(diag_paths ? nseq : 0);
+    uint64_t bytes = 0, bpn = 0, cmn = 0, hrn = 0, ckn = 0, pmn = 0, prn = 0, pcn = 0, fcn = 0, dcn = 0;
     for (uint32_t q = 0; q < nseq; ++q) {
         if (offs[q + 1] < offs[q]) throw Error(SVH_E_INVALID, "offsets must be non-decreasing");
         const uint64_t len = offs[q + 1] - offs[q];
@@ -1630,6 +1652,18 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
                 pcn += pipe_ckpt_floats(len, ppl->plan.P);
                 h_fcoff[q] = fcn;
                 fcn += pipe_fck_floats(len);
+            } else if (dpl) {  // (prn counts floats here: the ranges' minima)
+                const uint32_t nr = dpl->plan.nrng;
+                h_pmoff[q] = pmn;
+                pmn += diag_mask_words(len, nr);
+                h_proff[q] = prn;
+                prn += diag_mu_floats(len, nr);
+                h_pcoff[q] = pcn;
+                pcn += diag_ckpt_floats(len, nr);
+                h_fcoff[q] = fcn;
+                fcn += pipe_fck_floats(len);
+                h_dcoff[q] = dcn;
+                dcn += diag_cck_floats(len, nr);
             }
         } else if (paths) {
             h_bpoff[q] = bpn;
@@ -1657,11 +1691,12 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     };
     const Section s_sym = section(bytes), s_symoff = section((size_t)nseq * 8), s_begin = section((size_t)nseq * 4),
                   s_end = section((size_t)nseq * 4);
-    const bool cp = paths && chain_paths, pp = cp && pipe_paths, fp = paths && !chain_paths;
+    const bool cp = paths && chain_paths, pp = cp && recs, dgp = cp && diag_paths, fp = paths && !chain_paths;
     const Section s_path = section(paths ? (size_t)nseq * 8 : 0), s_cm = section(cp ? (size_t)nseq * 8 : 0),
                   s_hr = section(cp ? (size_t)nseq * 8 : 0), s_ck = section(cp ? (size_t)nseq * 8 : 0),
                   s_pm = section(pp ? (size_t)nseq * 8 : 0), s_pr = section(pp ? (size_t)nseq * 8 : 0),
                   s_pc = section(pp ? (size_t)nseq * 8 : 0), s_fc = section(pp ? (size_t)nseq * 8 : 0),
+                  s_dc = section(dgp ? (size_t)nseq * 8 : 0),
                   s_bp = section(fp ? (size_t)nseq * 8 : 0);
     static const bool trace = std::getenv("SVH_TRACE_ONESHOT") && std::atoi(std::getenv("SVH_TRACE_ONESHOT"));
     const auto tl0 = std::chrono::steady_clock::now();
@@ -1720,6 +1755,7 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     put(s_pr, h_proff.data());
     put(s_pc, h_pcoff.data());
     put(s_fc, h_fcoff.data());
+    put(s_dc, h_dcoff.data());
     put(s_bp, h_bpoff.data());
     const auto tl1 = std::chrono::steady_clock::now();
     d_in.reserve(in_bytes);
@@ -1744,6 +1780,7 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     p_proff = u64p(s_pr);
     p_pcoff = u64p(s_pc);
     p_fcoff = u64p(s_fc);
+    p_dcoff = u64p(s_dc);
     p_bpoff = u64p(s_bp);
     // results: fault word | best states | scores, one device arena (read() copies it at once); a
     // grown arena starts with a clear fault word
@@ -1762,9 +1799,10 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
         d_ckpt.reserve((size_t)std::max<uint64_t>(ckn, 1) * 4);
         if (pp) {
             d_pmask.reserve((size_t)std::max<uint64_t>(pmn, 1) * 4);
-            d_prec.reserve((size_t)std::max<uint64_t>(prn, 1) * 8);
+            d_prec.reserve((size_t)std::max<uint64_t>(prn, 1) * (dgp ? 4 : 8));
             d_pck.reserve((size_t)std::max<uint64_t>(pcn, 1) * 4);
             d_fck.reserve((size_t)std::max<uint64_t>(fcn, 1) * 4);
+            if (dgp) d_dcc.reserve((size_t)std::max<uint64_t>(dcn, 1) * 4);
         }
     } else if (fp) {
         d_bp.reserve((size_t)std::max<uint64_t>(bpn, 1) * 2);
@@ -1874,6 +1912,35 @@ void Batch::run(uint32_t level, hipStream_t s) {
             hip_check(launch_chain_traceback(bpl->view, cb, p_pathoff, d_paths.as<int32_t>(), s),
                       "chain traceback kernel (pipe paths fallback)");
         }
+        pipe_ran = true;
+    } else if (level <= 1 && diag_paths) {
+        // decoded paths on the diagonal plan: the same four launches -- its path variant, the chain
+        // path variant for rows whose speculation failed, the diagonal traceback (unflagged rows),
+        // the chain traceback (flagged rows)
+        const DevicePipePlan* dpl = model->diag_paths_for(nseq);
+        const DeviceBandPlan* bpl = model->band_for(true);
+        if (!dpl || !bpl) throw Error(SVH_E_STATE, "batch planned for diagonal paths, model has no such plan");
+        pipe.ensure(nseq, dpl->plan.nrng, s);
+        FusedBatch pb = fb;
+        pb.cmask = d_pmask.as<uint32_t>();
+        pb.cmask_off = p_pmoff;
+        pb.ckpt = d_pck.as<float>();
+        pb.ckpt_off = p_pcoff;
+        pb.prec = d_prec.as<float2>();  // floats [nrng][len] per sequence, offsets in floats
+        pb.prec_off = p_proff;
+        pb.fck = d_fck.as<float>();
+        pb.fck_off = p_fcoff;
+        pb.hrec = d_dcc.as<uint32_t>();  // floats [nrng][checkpoints] per sequence
+        pb.hrec_off = p_dcoff;
+        pb.pipe = &pipe.view;
+        hip_check(launch_diag(dpl->view, pb, pipe.view, s), "diagonal Viterbi kernel (paths)");
+        FusedBatch cb = fb;  // chain buffers
+        cb.run_mask = pipe.view.viol;
+        hip_check(launch_chain(bpl->view, 1, cb, s), "chain Viterbi kernel (diagonal paths fallback)");
+        hip_check(launch_diag_traceback(dpl->view, pb, p_pathoff, d_paths.as<int32_t>(), pipe.view.viol, s),
+                  "diagonal traceback kernel");
+        hip_check(launch_chain_traceback(bpl->view, cb, p_pathoff, d_paths.as<int32_t>(), s),
+                  "chain traceback kernel (diagonal paths fallback)");
         pipe_ran = true;
     } else if (level <= 1) {
         launch_step_kernel(fb, paths);

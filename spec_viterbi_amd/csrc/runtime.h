@@ -264,6 +264,10 @@ struct Model {
     // Pipelined plan for a decoded-path pass over nseq rows (nullptr: the chain / fused variant):
     // the latency plan, with the chain kernel's path variant as the fallback of flagged rows.
     const DevicePipePlan* pipe_paths_for(uint32_t nseq) const;
+    // Diagonal plan for a decoded-path pass (diag.hip PATHS, nullptr: none): only for models created
+    // with SVH_KERNEL_DIAG whose F wins every tie and feeds no term to S, whose walk fits the traceback's LDS and whose path
+    // variant keeps two workgroups per CU; the chain path variant is the fallback of flagged rows.
+    const DevicePipePlan* diag_paths_for(uint32_t nseq) const;
     void spec_build(uint32_t level, hipStream_t s);
     svh_model_info info(uint32_t nseq = 0, bool paths = false, uint32_t level = 0) const;
     // one pass of the step kernel the model plans for (chain, band, fused or generic)
@@ -285,7 +289,7 @@ struct Batch {
     uint64_t* p_symoff = nullptr;
     uint32_t *p_begin = nullptr, *p_end = nullptr;
     uint64_t *p_pathoff = nullptr, *p_cmoff = nullptr, *p_hroff = nullptr, *p_ckoff = nullptr, *p_pmoff = nullptr,
-             *p_proff = nullptr, *p_pcoff = nullptr, *p_fcoff = nullptr, *p_bpoff = nullptr;
+             *p_proff = nullptr, *p_pcoff = nullptr, *p_fcoff = nullptr, *p_dcoff = nullptr, *p_bpoff = nullptr;
     // results: one device arena {fault word (16 B) | best states | scores}: read() copies it once.
     // The fault word (FusedBatch::fault; kFault* bits) is written only by this batch's kernels
     // and read and cleared only by this batch.
@@ -300,6 +304,11 @@ struct Batch {
     // checkpoints (the heavy records share d_hrec: the chain fallback writes only flagged rows)
     bool pipe_paths = false;
     DeviceBuffer d_pmask, d_prec, d_pck, d_fck;
+    // paths on the diagonal plan (diag.hip PATHS; never together with pipe_paths): its decision words,
+    // range minima, checkpoints and F checkpoints in the four buffers above (kernels.h gives the
+    // layouts), the ranges' sink checkpoints in d_dcc
+    bool diag_paths = false;
+    DeviceBuffer d_dcc;
     PipeScratchBuffers pipe;  // pipelined kernel scratch (sized for the rows of each launch)
 
     // _spec runs
@@ -319,7 +328,7 @@ struct Batch {
     // host tables of the last load (copied into h_in)
     Pinned<uint8_t> h_out;  // read(): the result arena and the paths land here in one sync
     std::vector<uint64_t> h_symoff, h_pathoff, h_bpoff, h_cmoff, h_hroff, h_ckoff;
-    std::vector<uint64_t> h_pmoff, h_proff, h_pcoff, h_fcoff;
+    std::vector<uint64_t> h_pmoff, h_proff, h_pcoff, h_fcoff, h_dcoff;
 
     Batch(Model* m, uint64_t nseq, const uint64_t* offsets, const uint64_t* symbols, uint32_t flags);
     Batch(Model* m, uint64_t nseq, const uint64_t* offsets, const uint8_t* symbols, uint32_t flags);
