@@ -157,6 +157,11 @@ typedef struct {
                                      SVH_PIPE_MAX_NSEQ override applies to scores only) */
     int32_t diag_ranges;   /* diagonal plan (SVH_KERNEL_DIAG): ranges of 64 diagonals per sequence, 0 = none */
     uint32_t diag_max_nseq; /* AUTO runs it for scores-only batches of at most this many sequences */
+    int32_t diag_sm;       /* svh_batch_plan: diagonals per lane of the batch's diagonal-plan launch (1, or 2:
+                              ranges of 128 diagonals, for batches that would put more than one wave on a
+                              SIMD; at level >= 2 the tail's launch), 0 = the batch does not run that plan.
+                              The environment variable SVH_DIAG_SM = 1 / 2, read when a model is created,
+                              forces either for every scores launch of that model (appended in ABI 4) */
 } svh_model_info;
 /* The model's plan for a one-sequence scores-only run (kernel/threads/slots describe it). */
 int svh_model_get_info(svh_model_t m, svh_model_info* info);

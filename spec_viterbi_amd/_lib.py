@@ -64,6 +64,7 @@ class svh_model_info(ctypes.Structure):
         ("pipe_max_nseq_paths", c_uint32),
         ("diag_ranges", c_int32),
         ("diag_max_nseq", c_uint32),
+        ("diag_sm", c_int32),
     ]
 
 

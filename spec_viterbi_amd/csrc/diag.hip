@@ -61,6 +61,8 @@ constexpr uint32_t kDK = SVH_DIAG_K;  // steps per block (= columns per ring gro
 static_assert(kDK == 32 || kDK == 64, "block length");
 constexpr uint32_t kDR = 5 * kDK;     // ring columns (five groups of kDK)
 constexpr uint32_t kDRS = kDR + 64;   // slots per symbol plane: the ring and a mirror of its first 64
+constexpr uint32_t kDRS2 = kDR + 128; // two diagonals per lane: floats per ea / eb plane (a mirror of the first 128)
+static_assert(kDRS2 % 64 == 0, "the eb plane and the second diagonal lie whole multiples of 64 floats behind the lane's ea");
 constexpr uint32_t kDG = kDR / kDK;   // ring groups
 constexpr uint32_t kCP = kDK / 2;     // 16-byte chunks of a plane's group (two columns each)
 constexpr uint32_t kDE = 4;           // floats per entry of the constants stream
@@ -98,12 +100,20 @@ constexpr uint32_t kDMaxSym = 32;
 #ifndef SVH_DIAG_PAB
 #define SVH_DIAG_PAB 0
 #endif
+// SVH_DIAG_CMPX2 (A/B of the two-diagonal step's check): 1 = v_cmpx as everywhere else, 0 = a compare
+// and an add with carry into a per-lane count, read at the row's end
+#ifndef SVH_DIAG_CMPX2
+#define SVH_DIAG_CMPX2 1
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif
 
 __device__ __forceinline__ f2 lds_ld2(uint32_t a) {
     return *(const __attribute__((address_space(3))) f2*)(size_t)a;
+}
+__device__ __forceinline__ float lds_ld1(uint32_t a) {
+    return *(const __attribute__((address_space(3))) float*)(size_t)a;
 }
 
 // The speculation check, one VALU: EXEC &= !(a < b) (v_cmpx writes VCC and EXEC).  A lane whose
@@ -132,10 +142,10 @@ __device__ __forceinline__ void exec_collect(uint64_t& alive) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx) {
-    // ring [S][kDRS] float2 | symbol template [S][8] | constants [W][2][kDK][kDE] | ring addresses [W][2][kDK] |
-    // X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
-    return ((size_t)S * kDRS * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
+__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1) {
+    // ring [S][kDRS] float2 (dm = 2: [S][2][kDRS2] floats) | symbol template [S][8] | constants [W][2][kDK][kDE] |
+    // ring addresses [W][2][kDK] | X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
+    return ((size_t)S * (dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
 }
 
 // Decoded paths (PATHS; the walk is pipe_paths.hip's diag entry): fold ring [W][kFS][64] floats behind
@@ -154,13 +164,28 @@ __host__ __device__ constexpr size_t diag_lds_paths(uint32_t W, uint32_t S, bool
 // all-lanes work follows an exec_collect() of its own (one per kFS steps): no lane is off in it.
 // Begin is 0 for every row; a row whose check failed is not re-run here (its path needs the chain
 // kernel's records: the host's fallback launch takes it, x.viol).
-template <int W, bool SX, bool PATHS = false>
+//
+// DM = 2 (scores only): two diagonals per lane.  Lane l of range r (128 wide: NR = nrng2, NP = 128 NR
+// = P) holds diagonals 128 r + l and 128 r + 64 + l, so a wave pays the step's per-wave part -- the
+// constants read, the address add, the check, the {F, c} advance, the sink minimum, the scalar work
+// and the wait -- once for 128 positions.  The check and the sink take m = min(x_a, x_b): fl(a + .)
+// is monotone, so fl(A_F + m) < F' iff it holds for one of the two positions, and the per-lane sink
+// recurrence driven by m still has the row's S as its minimum over lanes (the argument above over a
+// coarser partition of the positions).  The ring holds an ea and an eb plane per symbol
+// ([S][2][kDRS2] floats, a mirror of the first 128 columns behind the ring), so that one two-address
+// read per plane yields {ea_a, ea_b} / {eb_a, eb_b} as register pairs and the chain and feeder
+// terms are one packed add each; the lanes of a block walk through four ring groups instead of
+// three, which the five groups still hold (group kb + 4 is written over group kb - 1).
+template <int W, bool SX, bool PATHS = false, int DM = 1>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
+    static_assert(DM == 1 || (DM == 2 && !PATHS), "decoded paths keep one diagonal per lane");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const uint32_t S = m.S, NR = m.nrng, NP = NR * 64, P = m.P;
-    float* ring = lds;                                   // [S][kDRS] {ea, eb}
-    float* hcr = ring + (size_t)S * kDRS * 2;            // [S][8] stream template of symbol o
+    constexpr uint32_t RW = 64 * DM;                     // diagonals (positions) per range
+    constexpr uint32_t RS = DM == 2 ? kDRS2 : kDRS;      // pairs of floats per symbol in the ring
+    const uint32_t S = m.S, NR = DM == 2 ? m.nrng2 : m.nrng, NP = NR * RW, P = m.P;
+    float* ring = lds;                                   // [S][kDRS] {ea, eb}; DM = 2: [S][2][kDRS2]
+    float* hcr = ring + (size_t)S * RS * 2;              // [S][8] stream template of symbol o
     float* strm = hcr + S * 8;                           // [W][2][kDK] {A_F, A_S, X_FF, X_SS}
     float* adr = strm + W * 2 * kDK * kDE;               // [W][2][kDK] ring address of (o_t, step)
     float* xsf = adr + W * 2 * kDK;                      // [W][2][kDK] X_SF (SX only)
@@ -184,7 +209,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         else if (k == 2) v = h[3];
         else if (k == 3) v = h[2];
         else if (k == 4) v = SX ? h[4] : kInf;
-        else if (k == 5) v = __builtin_bit_cast(float, ring_a + o * kDRS * 8u);
+        else if (k == 5) v = __builtin_bit_cast(float, ring_a + o * RS * 8u);
         hcr[i] = v;
     }
 
@@ -207,12 +232,14 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     typedef float lvec __attribute__((ext_vector_type(4 * kRep)));  // a vector, not an array: stays in VGPRs
     lvec lreg;
     auto gload = [&](uint32_t g) {
-        const uint32_t c0 = (rg * 64 + g * kDK) % NP;
+        const uint32_t c0 = (rg * RW + g * kDK) % NP;
 #pragma unroll
         for (uint32_t r = 0; r < kRep; ++r) {
             // unconditional (clamped) loads: the registers stay registers
             const uint32_t k = min(tid + r * kT, nchunk - 1);
-            const float4 v = *reinterpret_cast<const float4*>(m.dtab + (size_t)(k / kCP) * NP + c0 + 2 * (k % kCP));
+            // (DM = 2: a symbol's kCP chunks are its ea plane's kCP / 2, four columns each, then its eb plane's)
+            const float4 v = DM == 2 ? *reinterpret_cast<const float4*>(m.dtab2 + (size_t)(k / (kCP / 2)) * NP + c0 + 4 * (k % (kCP / 2)))
+                                     : *reinterpret_cast<const float4*>(m.dtab + (size_t)(k / kCP) * NP + c0 + 2 * (k % kCP));
             lreg[4 * r] = v.x;
             lreg[4 * r + 1] = v.y;
             lreg[4 * r + 2] = v.z;
@@ -225,10 +252,11 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         for (uint32_t r = 0; r < kRep; ++r) {
             const uint32_t k = tid + r * kT;
             if (k < nchunk) {
-                float* d = ring + ((size_t)(k / kCP) * kDRS + s0 + 2 * (k % kCP)) * 2;
+                float* d = DM == 2 ? ring + (size_t)(k / (kCP / 2)) * kDRS2 + s0 + 4 * (k % (kCP / 2))
+                                   : ring + ((size_t)(k / kCP) * kDRS + s0 + 2 * (k % kCP)) * 2;
                 const float4 v = make_float4(lreg[4 * r], lreg[4 * r + 1], lreg[4 * r + 2], lreg[4 * r + 3]);
                 *reinterpret_cast<float4*>(d) = v;
-                if (s0 < 64) *reinterpret_cast<float4*>(d + kDR * 2) = v;
+                if (s0 < RW) *reinterpret_cast<float4*>(d + kDR * (DM == 2 ? 1 : 2)) = v;
             }
         }
     };
@@ -248,7 +276,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             const uint32_t i = kb * kDK + 1 + lane;
             const uint32_t e = (w * 2 + (kb & 1u)) * kDK + lane;
             *reinterpret_cast<float4*>(strm + e * kDE) = h0;
-            adr[e] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + (i % kDR) * 8u);
+            adr[e] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + (i % kDR) * (DM == 2 ? 4u : 8u));
             if (SX) xsf[e] = h1.x;
         }
     };
@@ -294,18 +322,23 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     }
 
     // ---- state at observation first - 1
-    float xv = kInf, F = kInf, c = kInf;
+    float xv = kInf, xv2 = kInf, F = kInf, c = kInf;  // (xv2: the lane's second diagonal, DM = 2)
     uint64_t alive = ~0ull;  // lanes whose check has held so far (collected from EXEC after every block)
     if (real && beg == 0) {
         const uint32_t o0 = (uint32_t)uniform((int)sym[0]);
-        const uint32_t p = rg * 64 + lane;
+        const uint32_t p = rg * RW + lane;
         xv = m.e0[(size_t)o0 * P + p] + m.start[p];
+        if (DM == 2) xv2 = m.e0[(size_t)o0 * P + p + 64] + m.start[p + 64];
         F = m.rowF >= 0 ? m.hc[o0 * 8 + 5] + m.startF : kInf;
         c = (rg == 0 && lane == 0 && m.rowS >= 0) ? m.hc[o0 * 8 + 6] + m.startS : kInf;
     } else if (real) {  // resumed row (the _spec tail, time-parallel segments): scores of first-1
         const float* vin = b.v_in + (size_t)b.v_in_row[q] * m.n;
-        const uint32_t r = m.lrow[rg * 64 + lane];
+        const uint32_t r = m.lrow[rg * RW + lane];
         xv = r != kNoRow ? vin[r] : kInf;
+        if (DM == 2) {
+            const uint32_t r2 = m.lrow[rg * RW + 64 + lane];
+            xv2 = r2 != kNoRow ? vin[r2] : kInf;
+        }
         F = m.rowF >= 0 ? vin[m.rowF] : kInf;
         c = (rg == 0 && lane == 0 && m.rowS >= 0) ? vin[m.rowS] : kInf;
     }
@@ -331,7 +364,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     // in registers (slot j % kNS, j % kNE)
     typedef float hvec __attribute__((ext_vector_type(4 * kNS)));
     typedef float avec __attribute__((ext_vector_type(2 * kAG)));
-    typedef float evec __attribute__((ext_vector_type(2 * kNE)));
+    typedef float evec __attribute__((ext_vector_type(2 * DM * kNE)));
     hvec hq;
     avec aq, xq;  // ring addresses / X_SF of two groups of kAG steps (slot group % 2)
     evec eq;
@@ -360,6 +393,14 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         // (the element copied to a scalar first: __builtin_bit_cast of an ext-vector element lvalue
         // reads the vector's first element)
         const float roff = aq[j % (2 * kAG)];
+        if constexpr (DM == 2) {  // {ea_a, ea_b}, {eb_a, eb_b}: one two-address read per plane
+            const uint32_t a = __builtin_bit_cast(uint32_t, roff) + lane * 4u;
+            eq[4 * (j % kNE)] = lds_ld1(a);
+            eq[4 * (j % kNE) + 1] = lds_ld1(a + 256u);
+            eq[4 * (j % kNE) + 2] = lds_ld1(a + kDRS2 * 4u);
+            eq[4 * (j % kNE) + 3] = lds_ld1(a + kDRS2 * 4u + 256u);
+            return;
+        }
         const f2 e = lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u);
         eq[2 * (j % kNE)] = e.x;
         eq[2 * (j % kNE) + 1] = e.y;
@@ -390,6 +431,26 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         XP.x = fminf(zb, za);
         FC = (f2){Wv.x, cn};
         if constexpr (PATHS && SVH_DIAG_PAB != 2) fr_wr[slot * 64] = XP.x;
+    };
+    // DM = 2: the scores of the lane's two diagonals as one pair, their minimum in a pair of its own
+    // (the source of the packed heavy terms)
+    f2 X2 = (f2){xv, xv2};
+    uint32_t nviol = 0;  // (SVH_DIAG_CMPX2 = 0: steps at which the lane's check failed)
+    auto step2 = [&](const float4& h, float xs, const f2& ea, const f2& eb) {
+        XP.x = fminf(X2.x, X2.y);             // m: what the check and the sink need of the two scores
+        const f2 Y = XP.xx + (f2){h.x, h.y};  // {A_F + m, A_S + m}
+        const f2 Wv = FC + (f2){h.z, h.w};    // {F' = X_FF + F, X_SS + c}
+        const f2 za = ea + FC.xx;             // {ea_a + F, ea_b + F}
+        const f2 zb = eb + X2;                // {eb_a + x_a, eb_b + x_b}
+        // (the compiler puts this minimum into Y's pair and moves F' beside it, one v_mov per step
+        // that the one-diagonal step does not have; tying the minimum to Wv's second register with an
+        // asm statement made it two moves and 2.5 % slower)
+        float cn = fminf(Wv.y, Y.y);
+        if (SX) cn = fminf(cn, xs + FC.x);    // X_SF + F
+        if (SVH_DIAG_CMPX2) check_off(Y.x, Wv.x);
+        else nviol += Y.x < Wv.x ? 1u : 0u;
+        X2 = (f2){fminf(zb.x, za.x), fminf(zb.y, za.y)};
+        FC = (f2){Wv.x, cn};
     };
     // PATHS, after an exec_collect: the last n <= kFS steps' scores (observations t0 .. t0 + n - 1) ->
     // the range's light minima.  Lane l takes lanes 8 (l % 8) .. + 7 of step l / 8; three DPP stages
@@ -482,7 +543,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             const uint32_t a = SVH_DIAG_AB == 1 ? 0u : j % kNS, b2 = j % kNE;
             const float4 h = make_float4(hq[4 * a], hq[4 * a + 1], hq[4 * a + 2], hq[4 * a + 3]);
             const float xs = SX ? xq[SVH_DIAG_AB == 1 ? 0u : j % (2 * kAG)] : 0.0f;
-            const f2 e = (f2){eq[2 * b2], eq[2 * b2 + 1]};
+            const f2 e = DM == 2 ? (f2){eq[4 * b2], eq[4 * b2 + 1]} : (f2){eq[2 * b2], eq[2 * b2 + 1]};
             // at even steps, together: the constants of steps j + kPS and j + kPS + 1 (the next block's
             // past kDK - 1), then the ring pairs of steps j + kPE and j + kPE + 1, then, every kAG
             // steps, the ring addresses of steps j + 2 kAG .. (into the slot of the group whose last
@@ -506,12 +567,14 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
                     if (SX) gread(xq, xsf, kb, j + kAG);
                 }
                 if (SVH_DIAG_AB == 0) {
-                    // lgkmcnt(5 or 6) alone (PATHS: and the two ring writes since the pairs' reads)
-                    __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0)) << 8));
+                    // lgkmcnt(5 or 6) alone (PATHS: and the two ring writes since the pairs' reads;
+                    // DM = 2: the pairs of two steps are four reads)
+                    __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0) + (DM == 2 ? 2 : 0)) << 8));
                     __builtin_amdgcn_sched_barrier(0);                         // ahead of both steps' uses
                 }
             }
-            step(h, xs, e, j % kFS);
+            if constexpr (DM == 2) step2(h, xs, e, (f2){eq[4 * b2 + 2], eq[4 * b2 + 3]});
+            else step(h, xs, e, j % kFS);
             if (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // keep the reads where they are issued
             if constexpr (PATHS) {
                 if (j % kFS == kFS - 1 && (SVH_DIAG_PAB != 4 || j == kDK - 1)) {
@@ -554,7 +617,13 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         for (uint32_t j = 0; j < rem; ++j) {
             const float4 h = *reinterpret_cast<const float4*>(strm + (e0 + j) * kDE);
             const float roff = adr[e0 + j];
-            step(h, SX ? xsf[e0 + j] : 0.0f, lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u));
+            if constexpr (DM == 2) {
+                const uint32_t a = __builtin_bit_cast(uint32_t, roff) + lane * 4u;
+                step2(h, SX ? xsf[e0 + j] : 0.0f, (f2){lds_ld1(a), lds_ld1(a + 256u)},
+                      (f2){lds_ld1(a + kDRS2 * 4u), lds_ld1(a + kDRS2 * 4u + 256u)});
+            } else {
+                step(h, SX ? xsf[e0 + j] : 0.0f, lds_ld2(__builtin_bit_cast(uint32_t, roff) + lane * 8u));
+            }
         }
         exec_collect(alive);  // right behind the loop's scalar branch: no other branch sees a partial EXEC
     };
@@ -576,9 +645,11 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         if (SVH_DIAG_AB != 3) lds_barrier();
     }
 
+    if (DM == 2 && !SVH_DIAG_CMPX2) alive &= __builtin_amdgcn_ballot_w64(nviol == 0);
     F = FC.x;
     c = FC.y;
-    xv = XP.x;
+    xv = DM == 2 ? X2.x : XP.x;
+    xv2 = X2.y;
 
     // ---- scores of the light positions and this wave's partials
 #if SVH_DIAG_AB == 5  // diagnostics: the scores only (every wave leaves here)
@@ -612,7 +683,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     uint32_t last = 0;
     if (real) {
         float* out = b.scores + (size_t)q * m.n;
-        const uint32_t pe = (rg * 64 + lane + nst) % NP;
+        const uint32_t pe = (rg * RW + lane + nst) % NP;
         const uint32_t r = m.lrow[pe];
         float bv = kInf;
         uint32_t bk = kNoRow;
@@ -620,6 +691,13 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             g_st_score(out + r, xv);  // the row's re-run may come from another XCD
             bv = xv;
             bk = r;
+        }
+        if constexpr (DM == 2) {  // the second diagonal, 64 positions on
+            const uint32_t r2 = m.lrow[pe + 64 >= NP ? pe + 64 - NP : pe + 64];
+            if (r2 != kNoRow) {
+                g_st_score(out + r2, xv2);
+                lex_min(bv, bk, xv2, r2);
+            }
         }
         wave_lexmin63(bv, bk);
         const float cmin = wave_min63(c);
@@ -722,10 +800,10 @@ __global__ __launch_bounds__(256) void diag_finish_kernel(PipeModel m, FusedBatc
     if (*flag) pipe_rerun_row<2, 4, SX>(m, b, q, lds);
 }
 
-template <int W>
+template <int W, int DM = 1>
 const void* diag_ptr(bool sx) {
-    return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true>)
-              : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false>);
+    return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, DM>)
+              : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM>);
 }
 // (Only the instantiations without X_SF: with both PATHS and SX the block's body is past the
 // compiler's limit for `#pragma unroll`, the 64 steps are then unrolled in part, the register
@@ -741,14 +819,22 @@ const void* diag_paths_ptr() {
 
 uint32_t diag_waves_for(uint64_t nseq) { return nseq >= 4 ? 4u : nseq >= 2 ? 2u : 1u; }
 
-static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx) {
+static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1) {
     const size_t rerun = (2 * (size_t)P + 2 * W) * 4;  // pipe_rerun_row: v[2][P], red[2][W]
-    const size_t mainb = diag_lds_main(W, S, sx);
+    const size_t mainb = diag_lds_main(W, S, sx, dm);
     return mainb > rerun ? mainb : rerun;
 }
 
 // (the larger of the two kernels': models that use X_SF keep one stream more)
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P) { return diag_lds(W, S, P, true); }
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm) { return diag_lds(W, S, P, true, dm); }
+
+uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
+    if (paths || !m.dtab2 || !m.nrng2 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) return 1;
+    if (m.dsm == 1 || m.dsm == 2) return m.dsm;
+    if (resumed || !m.cus) return 1;
+    const uint64_t W = diag_waves_for(nseq);
+    return (nseq + W - 1) / W * W * m.nrng > 4ull * m.cus ? 2 : 1;
+}
 
 size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx) { return diag_lds_paths(W, S, sx); }
 
@@ -772,11 +858,15 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
         return hipErrorInvalidValue;
     if (b.nseq == 0) return hipSuccess;
     const uint32_t W = diag_waves_for(b.nseq);
-    const void* fn = paths ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
-                           : (W == 4 ? diag_ptr<4>(m.sx != 0) : W == 2 ? diag_ptr<2>(m.sx != 0) : diag_ptr<1>(m.sx != 0));
-    size_t lds = paths ? diag_lds_paths(W, m.S, m.sx != 0) : diag_lds(W, m.S, m.P, m.sx != 0);
+    const uint32_t dm = diag_sm_for(m, b.nseq, b.v_in != nullptr, paths);
+    if (dm == 2 && ((size_t)m.nrng2 * 128 != m.P || x.G < m.nrng2)) return hipErrorInvalidValue;
+    const bool sx = m.sx != 0;
+    const void* fn = paths     ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
+                     : dm == 2 ? (W == 4 ? diag_ptr<4, 2>(sx) : W == 2 ? diag_ptr<2, 2>(sx) : diag_ptr<1, 2>(sx))
+                               : (W == 4 ? diag_ptr<4>(sx) : W == 2 ? diag_ptr<2>(sx) : diag_ptr<1>(sx));
+    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * m.nrng;
+    const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng);
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     // even placement: a launch that fits the chip gets its LDS request raised so that no CU can take
     // more than ceil(grid / CUs) of its workgroups (the dispatcher would otherwise stack up to four

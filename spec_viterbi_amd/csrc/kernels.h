@@ -229,6 +229,12 @@ struct PipeModel {
     unsigned long long* stamps;  // diagnostics (SVH_PIPE_DEBUG): [ticket][W][8] counters, or null
     uint32_t diag;               // diagnostics with stamps (SVH_PIPE_DEBUG bits > 1): 1 = no boundary
                                  // exchange (every wave runs as block 0; timing only, wrong results)
+    // diagonal plan, two diagonals per lane (diag.hip DM = 2): the same table split into planes,
+    // [S][2][128 nrng2] floats (ea plane, eb plane per symbol; 128 nrng2 = P), nrng2 ranges of 128
+    // diagonals per sequence; null: one diagonal per lane only
+    const float* dtab2;
+    uint32_t nrng2;
+    uint32_t dsm;           // SVH_DIAG_SM at model creation: 1 or 2 forces that many diagonals per lane, 0 = diag_sm_for's rule
 };
 constexpr int kPipeStamps = 15;  // written only by -DSVH_PIPE_DIAG builds of pipe.hip
 // Per-batch scratch of the pipelined kernel (sized for `rows` rows).
@@ -308,7 +314,13 @@ inline size_t pipe_path_lds_bytes(uint32_t W) { return (size_t)W * 8 * kPQuadStr
 // A workgroup is diag_waves_for(nseq) sequences x one range; rows whose speculation fails are re-run
 // in the same launch.  A scores row starts at observation 0 or resumes at begin > 0 from v_in.
 uint32_t diag_waves_for(uint64_t nseq);
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P);
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1);
+// Diagonals per lane of a scores launch (1 or 2).  Two -- ranges of 128 diagonals, half as many waves,
+// each paying the step's per-wave part once for 128 positions -- where one per lane would put more
+// than one wave on a SIMD: ceil(nseq / W) W nrng > 4 CUs.  Rows resumed from v_in (the _spec tail,
+// time-parallel segments) and path batches keep one.  PipeModel::dsm (SVH_DIAG_SM) forces either for
+// every scores launch.
+uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
 // Diagonal plan, decoded paths (diag.hip PATHS, pipe_paths.hip's diag walk).  Models whose F wins

@@ -713,9 +713,21 @@ PipePlan make_pipe_plan(const HostModel& hm, uint32_t sm, uint32_t waves, bool w
                 d[0] = e + sh.aw[0][p];
                 d[1] = e + sh.bw[p];
             }
+        // two diagonals per lane: ranges of 128 positions (128 nrng2 = P), the pairs split into an ea
+        // and an eb plane per symbol, which is what the kernel's ring refill copies as it stands
+        pp.nrng2 = (nL + 127) / 128;
+        const uint32_t NP2 = pp.nrng2 * 128;
+        pp.dtab2.assign((size_t)S * 2 * NP2, kInfH);
+        for (uint32_t p = 0; p < nL; ++p)
+            for (uint32_t o = 0; o < S; ++o) {
+                const float* d = pp.dtab.data() + ((size_t)o * NP + p) * 2;
+                pp.dtab2[((size_t)o * 2) * NP2 + p] = d[0];
+                pp.dtab2[((size_t)o * 2 + 1) * NP2 + p] = d[1];
+            }
         if (sh.bw[0] < kInfH) {  // cannot happen (analyze_band: p > 0), but the wrap depends on it
-            pp.nrng = 0;
+            pp.nrng = pp.nrng2 = 0;
             pp.dtab.clear();
+            pp.dtab2.clear();
         }
     }
     // decoded paths: term flags per position (as BandPlan::pflags with heavy feeder F) and the
@@ -816,6 +828,17 @@ void DevicePipePlan::upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream
         d_dtab.upload(p.dtab.data(), p.dtab.size() * 4, s);
         view.dtab = d_dtab.as<float2>();
         view.nrng = p.nrng;
+        if (p.nrng2 && !p.dtab2.empty() && (size_t)p.nrng2 * 128 == p.P &&
+            diag_lds_bytes(diag_waves_for(4), S, p.P, 2) <= 160 * 1024) {
+            d_dtab2.upload(p.dtab2.data(), p.dtab2.size() * 4, s);
+            view.dtab2 = d_dtab2.as<float>();
+            view.nrng2 = p.nrng2;
+        }
+        // SVH_DIAG_SM = 1 / 2: that many diagonals per lane for every scores launch (tests, A/B)
+        if (const char* e = std::getenv("SVH_DIAG_SM")) {
+            const int v = std::atoi(e);
+            view.dsm = v == 1 || v == 2 ? (uint32_t)v : 0u;
+        }
     }
     view.emax2 = p.emax2;
     // the pair-table step wherever it applies: TM = 4 (indexed operands, packed feeder terms:
@@ -1532,7 +1555,10 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         i.kernel = SVH_KERNEL_DIAG;
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
-        i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P);
+        i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
+        i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm);
+    } else if (!paths && level >= 2 && nseq && diag_for(nseq)) {  // the _spec tail's launch
+        i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, true, false);
     }
     if (paths && steps && level <= 1 && nseq && diag_paths_for(nseq)) {  // decoded paths on the diagonal plan
         const uint32_t w = diag_waves_for(nseq);
@@ -1540,6 +1566,7 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
         i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);
+        i.diag_sm = 1;
     }
     if (pipe.view.dtab) {
         i.diag_ranges = (int32_t)pipe.plan.nrng;

@@ -142,6 +142,9 @@ struct PipePlan {
     // diagonal plan (diag.hip; latency plan only): [S][64 nrng] float2 {ea, eb}, +inf past the light rows
     std::vector<float> dtab;
     uint32_t nrng = 0;
+    // ... two diagonals per lane: [S][2][128 nrng2] floats, ea plane then eb plane per symbol
+    std::vector<float> dtab2;
+    uint32_t nrng2 = 0;
     // _spec level 2 on this plan (pipe_l2.hip): the largest finite ea = fl(E_o[p] + aw_p), or +inf
     // when some score is negative (its margin check needs every score >= 0) or the plan is wide
     float emax2 = 0.0f;
@@ -156,7 +159,7 @@ PipePlan make_pipe_plan(const HostModel& hm, uint32_t sm = 0, uint32_t waves = 0
 
 struct DevicePipePlan {
     PipePlan plan;
-    DeviceBuffer d_tab, d_e0, d_start, d_lrow, d_hc, d_stamps, d_pflags, d_spos, d_dtab;
+    DeviceBuffer d_tab, d_e0, d_start, d_lrow, d_hc, d_stamps, d_pflags, d_spos, d_dtab, d_dtab2;
     PipeModel view{};
     void upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream_t s);
     void report_stamps(uint32_t nseq) const;  // diagnostic (SVH_PIPE_DEBUG): first sequence's waves
