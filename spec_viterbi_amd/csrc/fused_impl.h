@@ -18,7 +18,9 @@
 //     heavy rows, plus <= XM exception terms):  min_{k in U} fl(a + v[k]) == fl(a + min_{k in U}
 //     v[k]) for a = fl(E_h + w_h) because fp32 addition is monotone, so U costs one min per
 //     term, shared by every heavy row.  Bit-identical to the term-by-term form.
-//   * PATHS: per-step argmin backpointers (lowest predecessor index on ties) as uint16.
+//   * PATHS: per-step argmin backpointers (lowest predecessor index on ties) as uint16.  A heavy
+//     row's cell is stored once, by the heavy reduction (thread 0 one step late, thread h in the
+//     epilogue); the row's owner thread skips it in the light loop.
 #pragma once
 
 #include "device_common.h"
@@ -93,6 +95,17 @@ __global__ __launch_bounds__(kMaxFusedThreads) void fused_viterbi_kernel(FusedMo
                 else hk[h][s] = 0;
             }
         }
+    }
+
+    // PATHS: bit s = slot s of this thread is a heavy row.  Its backpointer cell belongs to the
+    // heavy reduction alone (thread 0 one step later, thread h in the epilogue); the owner must
+    // not store to it from the light loop: two waves' stores to one address would be ordered by
+    // nothing but the counted vmcnt before the barrier.
+    uint32_t hslots = 0;
+    if constexpr (PATHS) {
+#pragma unroll
+        for (int h = 0; h < HM; ++h)
+            if ((uint32_t)h < H && (uint32_t)hrow[h] % B == t) hslots |= 1u << ((uint32_t)hrow[h] / B);
     }
 
     // ---- sequence setup --------------------------------------------------------------------
@@ -282,7 +295,8 @@ __global__ __launch_bounds__(kMaxFusedThreads) void fused_viterbi_kernel(FusedMo
                     lex_min(r, rk, (e + lv[s][k]) + g[s][k], kx);
                 }
                 vn[j] = r;
-                if (j < n) bp[(size_t)(i - 1) * n + j] = (uint16_t)(rk == 0xFFFFFFFFu ? kNoPred : rk);
+                if (j < n && !((hslots >> s) & 1u))
+                    bp[(size_t)(i - 1) * n + j] = (uint16_t)(rk == 0xFFFFFFFFu ? kNoPred : rk);
             }
         }
 

@@ -1,14 +1,18 @@
 // Host code of the engine under AddressSanitizer + UBSan (built by `make tests`, run by
 // tests/test_readers_asan.py; no GPU is touched): the canonical host model and every plan builder
 // of runtime.cpp (fused, band / chain, pipelined latency and wide, on-chip level 2) over every
-// committed .chmm and over generated models with malformed and edge-case inputs, and the parser
+// committed .chmm and over generated models with malformed and edge-case inputs -- every fused plan
+// replayed on the host against the CSR recurrence (replay_fused_plan), with models aimed at each
+// fused family, the geometry edges and every workgroup cap -- and the parser
 // thread's chunk hand-off of the pipelined file decoder (chunker.cpp) over every .ess and the FASTA
 // fixture, with a consumer thread, at several chunkings, including files that fail mid-way.  The
 // counterpart of the reference running its whole test suite under valgrind memcheck
 // (run_tests.sh:4-7, tests/CMakeLists.txt:4-5).
 //   usage: test_host_asan <data dir> <fasta fixture> <scratch dir>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <dirent.h>
 #include <fstream>
 #include <limits>
@@ -79,16 +83,173 @@ int host_error(const Coo& c) {
     return 0;
 }
 
+bool same_bits(float a, float b) {  // bit-exact, except that -0.0 == +0.0
+    uint32_t x, y;
+    std::memcpy(&x, &a, 4);
+    std::memcpy(&y, &b, 4);
+    return x == y || (a == 0.0f && b == 0.0f);
+}
+
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+void lex_min(float& v, uint32_t& k, float v2, uint32_t k2) {  // (value, index) minimum, as the kernels'
+    if (v2 < v || (v2 == v && k2 < k)) v = v2, k = k2;
+}
+
+// One observation evaluated twice, for a few score vectors and every symbol: by the fused kernel's
+// schedule from the Plan tables alone (fused_impl.h: light rows from lcol / lval over the LDS index
+// space [states | +inf scratch | heavy slots], heavy rows from hval + exceptions, or hmask / hw +
+// exceptions in the uniform mode, emissions from emis_pad), and by the CSR recurrence
+// min_k fl(fl(E + T) + v[k]).  Values must agree bit for bit; in the general mode (the decoded-path
+// plan) the argmin predecessor too, lowest index on ties.
+// Returns what differs, or an empty string.
+std::string replay_difference(const svh::HostModel& hm, const svh::Plan& p) {
+    const uint32_t n = hm.n, S = hm.S, B = p.B, SM = p.SM, R = p.R, est = p.estride;
+    const uint32_t scratch = est, hs0 = est + 1;
+    const bool general = p.mode == svh::kHeavyGeneral;
+    const size_t ndma = (SM + 3) / 4;
+    bool sizes = est == SM * B && est >= n && B % 64 == 0 && B <= (uint32_t)svh::kMaxFusedThreads && p.H <= p.HM &&
+                 p.HM <= (uint32_t)svh::kMaxHeavy && p.XM <= (uint32_t)svh::kMaxExc && p.vstride >= hs0 + svh::kMaxHeavy &&
+                 p.vstride % 4 == 0 && p.lds_bytes == svh::fused_lds_bytes_for((int)SM, B, p.vstride) &&
+                 p.lds_bytes <= svh::kMaxLdsBytes && p.lcol.size() == (size_t)SM * R * B && p.lval.size() == p.lcol.size() &&
+                 p.emis_pad.size() >= (size_t)(S - 1) * est + ndma * B * 4 && p.start_pad.size() >= est;
+    if (general) sizes = sizes && p.hval.size() == (size_t)p.HM * SM * B && p.hvalid.size() == p.hval.size();
+    else sizes = sizes && p.hmask.size() == est;
+    if (!sizes) return "fused table sizes";
+    // what the padding must hold: +inf emissions and start scores past n, every LDS index in range
+    bool pads = true;
+    for (uint32_t o = 0; o < S; ++o)
+        for (uint32_t j = 0; j < est; ++j)
+            pads = pads && (j < n ? same_bits(p.emis_pad[(size_t)o * est + j], hm.emis[(size_t)o * n + j])
+                                  : std::isinf(p.emis_pad[(size_t)o * est + j]));
+    for (uint32_t j = 0; j < est; ++j) pads = pads && (j < n ? same_bits(p.start_pad[j], hm.start[j]) : std::isinf(p.start_pad[j]));
+    for (uint32_t c : p.lcol) pads = pads && c < p.vstride && (c < n || c >= scratch) && c < hs0 + std::max(p.H, 1u);
+    std::vector<int> hidx(n, -1);
+    for (uint32_t h = 0; h < (uint32_t)svh::kMaxHeavy; ++h) {
+        pads = pads && p.hrow[h] >= 0 && (uint32_t)p.hrow[h] < n;
+        if (h < p.H && pads) hidx[p.hrow[h]] = (int)h;
+        for (uint32_t x = 0; x < (uint32_t)svh::kMaxExc; ++x) {
+            const uint32_t c = p.xk[h][x];
+            pads = pads && c < p.vstride && (c < n || c >= scratch) && (h < p.H || (c == scratch && std::isinf(p.xw[h][x])));
+        }
+    }
+    if (!pads) return "fused padding and index ranges";
+
+    auto source_of = [&](uint32_t c) { return c == scratch ? kNone : c >= hs0 ? (uint32_t)p.hrow[c - hs0] : c; };
+    std::mt19937 rng(n * 131u + SM * 7u + p.family);
+    std::uniform_real_distribution<float> u(0.0f, 30.0f);
+    std::vector<float> v(n), lds(p.vstride);
+    for (int trial = 0; trial < 4; ++trial) {
+        for (float& x : v)
+            x = trial == 0 ? (rng() % 4 ? u(rng) : INFINITY)  // some +inf
+                : trial == 1 ? (float)(rng() % 3)            // exact ties
+                : trial == 2 ? (rng() % 16 ? INFINITY : u(rng))  // mostly +inf
+                             : INFINITY;
+        std::fill(lds.begin(), lds.end(), INFINITY);
+        std::copy(v.begin(), v.end(), lds.begin());
+        for (uint32_t h = 0; h < p.H; ++h) lds[hs0 + h] = v[p.hrow[h]];
+        float mu = INFINITY;  // uniform mode: the minimum over the shared source set
+        if (!general)
+            for (uint32_t k = 0; k < est; ++k) mu = std::fmin(mu, lds[k] + p.hmask[k]);
+        for (uint32_t o = 0; o < S; ++o) {
+            const float* e = p.emis_pad.data() + (size_t)o * est;
+            for (uint32_t j = 0; j < n; ++j) {
+                float ref = INFINITY, got = INFINITY;
+                uint32_t refk = kNone, gotk = kNone;
+                for (uint32_t q = hm.rowptr[j]; q < hm.rowptr[j + 1]; ++q)
+                    lex_min(ref, refk, (hm.emis[(size_t)o * n + j] + hm.val[q]) + v[hm.col[q]], hm.col[q]);
+                if (hidx[j] < 0) {
+                    const uint32_t s = j / B, t = j % B;
+                    for (uint32_t r = 0; r < R; ++r) {
+                        const size_t idx = ((size_t)s * R + r) * B + t;
+                        lex_min(got, gotk, (e[j] + p.lval[idx]) + lds[p.lcol[idx]], source_of(p.lcol[idx]));
+                    }
+                } else {
+                    const uint32_t h = (uint32_t)hidx[j];
+                    if (general) {
+                        for (uint32_t k = 0; k < est; ++k) {
+                            const size_t idx = ((size_t)h * SM + k / B) * B + k % B;
+                            lex_min(got, gotk, (e[j] + p.hval[idx]) + lds[k], p.hvalid[idx] ? k : kNone);
+                        }
+                    } else {
+                        got = (e[j] + p.hw[h]) + mu;
+                    }
+                    for (uint32_t x = 0; x < p.XM; ++x)
+                        lex_min(got, gotk, (e[j] + p.xw[h][x]) + lds[p.xk[h][x]], source_of(p.xk[h][x]));
+                }
+                if (!same_bits(got, ref) || (general && gotk != refk))
+                    return "fused schedule differs from the CSR recurrence at row " + std::to_string(j) + ", symbol " +
+                           std::to_string(o) + ", family " + std::to_string(p.family) + ": " + std::to_string(got) +
+                           " from " + std::to_string(gotk) + " vs " + std::to_string(ref) + " from " + std::to_string(refk);
+            }
+        }
+    }
+    // A minimum shows a wrong term only where that term wins, so the terms themselves too: every
+    // row's (source, weight) terms read back from the tables are exactly the CSR row, and every
+    // padding entry is inert (+inf weight).
+    auto wbits = [](float f) {
+        uint32_t b;
+        std::memcpy(&b, &f, 4);
+        return f == 0.0f ? 0u : b;
+    };
+    std::vector<std::pair<uint32_t, uint32_t>> terms;
+    for (uint32_t j = 0; j < n; ++j) {
+        terms.clear();
+        const std::string row = " of row " + std::to_string(j);
+        if (hidx[j] < 0) {
+            for (uint32_t r = 0; r < R; ++r) {
+                const size_t idx = ((size_t)(j / B) * R + r) * B + j % B;
+                if (p.lcol[idx] != scratch) terms.push_back({source_of(p.lcol[idx]), wbits(p.lval[idx])});
+                else if (!std::isinf(p.lval[idx])) return "finite weight on a padding term" + row;
+            }
+        } else {
+            const uint32_t h = (uint32_t)hidx[j];
+            for (uint32_t k = 0; k < est; ++k) {
+                const size_t idx = ((size_t)h * SM + k / B) * B + k % B;
+                if (general ? p.hvalid[idx] != 0 : p.hmask[k] == 0.0f) terms.push_back({k, wbits(general ? p.hval[idx] : p.hw[h])});
+                else if (!std::isinf(general ? p.hval[idx] : p.hmask[k])) return "finite heavy weight outside the pattern" + row;
+            }
+            for (uint32_t x = 0; x < p.XM; ++x) {
+                if (p.xk[h][x] != scratch) terms.push_back({source_of(p.xk[h][x]), wbits(p.xw[h][x])});
+                else if (!std::isinf(p.xw[h][x])) return "finite weight on a padding exception" + row;
+            }
+        }
+        std::sort(terms.begin(), terms.end());
+        bool same = terms.size() == hm.rowptr[j + 1] - hm.rowptr[j];
+        for (size_t x = 0; same && x < terms.size(); ++x) {
+            const uint32_t q = hm.rowptr[j] + (uint32_t)x;
+            same = terms[x].first == hm.col[q] && terms[x].second == wbits(hm.val[q]);
+        }
+        if (!same) return "the tables' terms differ from the CSR's" + row;
+    }
+    return "";
+}
+
+int plans_replayed = 0;
+void replay_fused_plan(const svh::HostModel& hm, const svh::Plan& p, const std::string& name) {
+    if (!p.fused) return;
+    ++plans_replayed;
+    const std::string diff = replay_difference(hm, p);
+    check(diff.empty(), name + ": " + diff);
+}
+
+// the fused planner at one workgroup cap: both variants, replayed
+void fused_plans(const svh::HostModel& hm, const std::string& name, int max_threads) {
+    for (bool uni : {true, false}) {
+        const svh::Plan p = svh::make_plan(hm, max_threads, uni);
+        ++plans_built;
+        if (p.fused) check(!p.emis_pad.empty() && !p.start_pad.empty(), name + ": fused tables");
+        if (p.fused && max_threads > 0) check(p.B <= (uint32_t)max_threads, name + ": workgroup cap");
+        if (!uni) check(!p.fused || p.mode == svh::kHeavyGeneral, name + ": path plan is term by term");
+        replay_fused_plan(hm, p, name + (uni ? " (scores plan)" : " (path plan)"));
+    }
+}
+
 // every plan builder over one model, with the invariants a launch relies on
 void plans(const svh::HostModel& hm, const std::string& name) {
     const uint32_t n = hm.n;
     check(hm.rowptr.size() == n + 1 && hm.rowptr[n] == hm.col.size() && hm.col.size() == hm.val.size(), name + ": CSR");
     for (uint32_t c : hm.col) check(c < n, name + ": column in range");
-    for (bool uni : {true, false}) {
-        const svh::Plan p = svh::make_plan(hm, 0, uni);
-        ++plans_built;
-        if (p.fused) check(!p.emis_pad.empty() && !p.start_pad.empty(), name + ": fused tables");
-    }
+    fused_plans(hm, name, 0);
     for (bool chain : {true, false}) {
         const svh::BandPlan b = svh::make_band_plan(hm, 0, chain);
         ++plans_built;
@@ -145,6 +306,41 @@ Coo generated(std::mt19937& rng, int kind) {
     return c;
 }
 
+// A model aimed at one fused family: every light row has R/2 + 1 .. R terms from random sources
+// (R itself for exact), H heavy rows take a term from every second or every state, each with its own
+// weight, plus terms from their fellow heavy rows and themselves (exception terms, up to XM = H).
+Coo aimed(std::mt19937& rng, uint64_t n, uint32_t R, uint32_t H, bool exact) {
+    std::uniform_real_distribution<float> u(0.0f, 8.0f);
+    Coo c;
+    c.n = n;
+    c.S = 3;
+    std::vector<uint64_t> heavy;
+    for (uint32_t h = 0; h < H; ++h) heavy.push_back(h == 0 ? n - 1 : (h * n) / (H + 1));
+    auto is_heavy = [&](uint64_t j) { return std::find(heavy.begin(), heavy.end(), j) != heavy.end(); };
+    for (uint64_t j = 0; j < n; ++j) {
+        if (is_heavy(j)) continue;
+        const uint32_t deg = std::min<uint64_t>(n, exact ? R : R / 2 + 1 + rng() % (R - R / 2));
+        const uint64_t first = rng() % n, stride = 1 + rng() % 7;  // distinct sources: gcd(stride, n) may exceed 1
+        std::vector<uint64_t> used;
+        for (uint64_t k = first; used.size() < deg; k = (k + stride) % n) {
+            while (std::find(used.begin(), used.end(), k) != used.end()) k = (k + 1) % n;
+            used.push_back(k);
+            c.src.push_back(k), c.dst.push_back(j), c.prob.push_back(rng() % 11 ? u(rng) : INFINITY);
+        }
+    }
+    for (size_t x = 0; x < heavy.size(); ++x) {
+        for (uint64_t k = x % 2; k < n; k += 1 + x % 2)
+            if (!is_heavy(k)) c.src.push_back(k), c.dst.push_back(heavy[x]), c.prob.push_back(u(rng));
+        for (size_t y = 0; y < heavy.size(); ++y)
+            if (y != x || x % 2 == 0) c.src.push_back(heavy[y]), c.dst.push_back(heavy[x]), c.prob.push_back(u(rng));
+    }
+    c.emis.resize(c.S * c.n);
+    for (float& e : c.emis) e = rng() % 13 ? u(rng) : INFINITY;
+    c.scol = {0, heavy.empty() ? 1 % n : heavy[0]};
+    c.sval = {u(rng), u(rng)};
+    return c;
+}
+
 // the parser thread's hand-off with a consumer thread: the sequences, in file order
 std::vector<std::vector<uint8_t>> chunked(const std::string& path, int fmt, uint64_t ms, uint64_t mx, size_t cap,
                                           int* err) {
@@ -194,6 +390,62 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 240; ++i) {
         const Coo c = generated(rng, i % 4);
         plans(host(c), "generated #" + std::to_string(i));
+    }
+    // models aimed at each fused family and at the geometry edges (n around SM * B, the largest
+    // fused model and the first one past it), at every workgroup cap
+    {
+        std::mt19937 r3(20261019);
+        int i = 0;
+        for (uint64_t n : {63, 64, 65, 511, 512, 513, 1024, 1025, 1600, 4096, 6143, 6144, 6145})
+            for (uint32_t R : {2u, 4u, 8u, 16u}) {
+                const uint32_t H = R == 2 ? (i % 2) * 2 : (uint32_t[]){0, 1, 4, 2}[i % 4];
+                const bool exact = i % 3 == 0;
+                ++i;
+                const svh::HostModel hm = host(aimed(r3, n, R, H, exact));
+                const std::string name = "aimed n=" + std::to_string(n) + " R=" + std::to_string(R) + " H=" + std::to_string(H);
+                const svh::Plan p = svh::make_plan(hm, 0, false);
+                const int fam = R == 2 ? svh::kFamR2 : R == 4 ? svh::kFamR4 : R == 8 ? svh::kFamR8 : svh::kFamR16;
+                check(p.fused == (n <= 6144), name + ": fused up to 6144 states");
+                if (p.fused) check(p.family == fam && p.H == H && p.R == R, name + ": family and heavy rows");
+                if (n == 6143 || n == 6144) check(p.SM == 12 && p.B == 512 && p.lds_bytes == 151952, name + ": largest geometry");
+                for (int threads : {64, 128, 256, 0}) fused_plans(hm, name + " threads=" + std::to_string(threads), threads);
+            }
+    }
+    // the replay itself: one wrong entry in a copy of any table of a plan must show
+    {
+        std::mt19937 r4(5);
+        const svh::HostModel hm = host(aimed(r4, 700, 4, 2, false));
+        const svh::Plan gen = svh::make_plan(hm, 0, false);
+        check(gen.fused && gen.H == 2 && gen.SM == 2 && replay_difference(hm, gen).empty(), "replay: the intact plan");
+        const uint32_t hr = (uint32_t)gen.hrow[1], est = gen.estride;
+        auto spoiled = [&](const char* what, auto&& edit) {
+            svh::Plan q = gen;
+            edit(q);
+            check(!replay_difference(hm, q).empty(), std::string("replay misses a wrong ") + what);
+        };
+        const size_t lterm = std::find_if(gen.lval.begin(), gen.lval.end(), [](float w) { return !std::isinf(w); }) - gen.lval.begin();
+        const size_t hterm = std::find(gen.hvalid.begin(), gen.hvalid.end(), 1) - gen.hvalid.begin();
+        spoiled("lval", [&](svh::Plan& q) { q.lval[lterm] += 0.5f; });
+        spoiled("lcol", [&](svh::Plan& q) { q.lcol[lterm] = q.lcol[lterm] == 3 ? 4 : 3; });
+        spoiled("lcol padding", [&](svh::Plan& q) { *std::find(q.lcol.begin(), q.lcol.end(), est) = est + 5; });
+        spoiled("hval", [&](svh::Plan& q) { q.hval[hterm] += 0.5f; });
+        spoiled("hvalid", [&](svh::Plan& q) { q.hvalid[hterm] = 0; });
+        spoiled("xk", [&](svh::Plan& q) { q.xk[0][0] = est; });
+        spoiled("xw", [&](svh::Plan& q) { q.xw[1][0] += 0.25f; });
+        spoiled("hrow", [&](svh::Plan& q) { q.hrow[1] = (int)(hr ? hr - 1 : 1); });
+        spoiled("emis_pad", [&](svh::Plan& q) { q.emis_pad[est + 7] += 1.0f; });
+        spoiled("emis_pad padding", [&](svh::Plan& q) { q.emis_pad[est - 1] = 0.0f; });
+        spoiled("estride", [&](svh::Plan& q) { q.estride += 64; });
+        const svh::HostModel chain = host(generated(r4, 0));
+        const svh::Plan uni = svh::make_plan(chain, 0, true);
+        check(uni.fused && uni.mode == svh::kHeavyUniform && replay_difference(chain, uni).empty(), "replay: the intact uniform plan");
+        for (int what = 0; what < 3; ++what) {
+            svh::Plan q = uni;
+            if (what == 0) q.hw[0] += 0.5f;
+            if (what == 1) q.hmask[1] = INFINITY;  // M_1 leaves the shared source set
+            if (what == 2) q.xw[0][0] += 0.5f;
+            check(!replay_difference(chain, q).empty(), "replay misses a wrong uniform table " + std::to_string(what));
+        }
     }
     // malformed inputs: the documented errors, never a crash or an out-of-bounds access
     {
@@ -262,7 +514,8 @@ int main(int argc, char** argv) {
         queue.stop();
         producer.join();
     }
-    std::printf("host asan: %zu models, %d plans built, %zu files chunked, %d failures\n", models.size(), plans_built,
-                files.size(), failures);
+    check(plans_replayed >= 2 * (int)models.size(), "every reference model has a fused plan to replay");
+    std::printf("host asan: %zu models, %d plans built, %d fused plans replayed, %zu files chunked, %d failures\n",
+                models.size(), plans_built, plans_replayed, files.size(), failures);
     return failures ? 1 : 0;
 }

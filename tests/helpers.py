@@ -154,3 +154,160 @@ def random_chain_hmm(L, S=20, seed=0, self_n=True, self_c=True, feed_c=False, c_
     return HMM(states_num=n, emit_num=S, trans_num=len(pr), trans_rows=np.array(src, np.uint64),
                trans_cols=np.array(dst, np.uint64), trans_probs=mod(pr), emissions=mod(em),
                start_probabilities_cols=st, start_probabilities=mod(rng.uniform(0.1, 1.0, size=st.size)))
+
+
+def regular_hmm(n, S=4, indeg=(2,), heavy=(), heavy_terms=1.0, heavy_heavy=0, self_loops=False, zero_emis=0.0,
+                ties=False, unreachable=0, start=None, nstart=2, inf_emis=(), seed=0):
+    """A random model with a controlled in-degree, so that a test can aim at one fused-kernel family.
+
+    Every light row's in-degree is drawn uniformly from `indeg` ({R}: exactly R; range(1, R + 1): up
+    to R); its sources are drawn without replacement over the whole state range (LDS gathers cross
+    slots and waves), and for every heavy row three light rows take it as a source.  `heavy` rows
+    receive a term from a fraction `heavy_terms` of the light states, each with its own random weight
+    (general, not uniform heavy rows), plus terms from their first `heavy_heavy` fellow heavy rows
+    and, with `self_loops`, from themselves (the kernels' exception terms).  `unreachable`: that many
+    light states (or the given ones) get no incoming term and no start entry; they still are sources.
+    `ties` draws every probability from {1/2, 1/4, 1/8}.  `start`: the start states (default: the
+    first `nstart` states that are not unreachable).  `inf_emis`: (state, symbol) pairs of
+    probability 0 on top of the random fraction `zero_emis`."""
+    from spec_viterbi_amd import HMM
+
+    rng = np.random.default_rng(seed)
+    heavy = tuple(int(h) for h in heavy)
+    is_heavy = np.zeros(n, bool)
+    is_heavy[list(heavy)] = True
+    light = np.nonzero(~is_heavy)[0]
+    if isinstance(unreachable, int):
+        unreachable = rng.choice(light, size=unreachable, replace=False) if unreachable else ()
+    dead = np.zeros(n, bool)
+    dead[list(unreachable)] = True
+    assert not (dead & is_heavy).any()
+    indeg = np.array(sorted(indeg))
+    assert indeg[-1] <= n
+
+    def prob(k):
+        if ties:
+            return rng.choice(np.array([0.5, 0.25, 0.125], np.float32), size=k)
+        return rng.uniform(0.01, 1.0, size=k).astype(np.float32)
+
+    src, dst = [], []
+    feeds = {}  # light row -> a heavy row it must take as a source
+    live = light[~dead[light]]
+    for h in heavy:
+        for j in rng.choice(live, size=min(3, live.size), replace=False):
+            feeds.setdefault(int(j), h)
+    for j in live:
+        k = rng.choice(n, size=int(rng.choice(indeg)), replace=False)
+        h = feeds.get(int(j))
+        if h is not None and k.size and h not in k:
+            k[0] = h
+        src.append(k)
+        dst.append(np.full(k.size, j))
+    for x, h in enumerate(heavy):
+        cnt = max(1, int(round(heavy_terms * light.size)))
+        k = [rng.choice(light, size=cnt, replace=False)]
+        others = [o for o in heavy if o != h]
+        k.append(np.array([others[(x + d) % len(others)] for d in range(min(heavy_heavy, len(others)))], np.int64))
+        if self_loops:
+            k.append(np.array([h]))
+        k = np.concatenate(k)
+        src.append(k)
+        dst.append(np.full(k.size, h))
+    src = np.concatenate(src) if src else np.zeros(0, np.int64)
+    dst = np.concatenate(dst) if dst else np.zeros(0, np.int64)
+    pr = prob(src.size)
+    em = prob(S * n).reshape(S, n)
+    if zero_emis > 0:
+        em[rng.random(em.shape) < zero_emis] = 0.0
+    for j, o in inf_emis:
+        em[o, j] = 0.0
+    if start is None:
+        start = np.nonzero(~dead)[0][:nstart]
+    st = np.array(start, np.uint64)
+    assert not dead[st.astype(np.int64)].any()
+
+    def mod(p):
+        p = np.asarray(p, np.float32)
+        with np.errstate(divide="ignore"):
+            return np.where(p > 0, -np.log2(p), np.inf).astype(np.float32)
+
+    return HMM(states_num=n, emit_num=S, trans_num=int(pr.size), trans_rows=src.astype(np.uint64),
+               trans_cols=dst.astype(np.uint64), trans_probs=mod(pr), emissions=mod(em),
+               start_probabilities_cols=st, start_probabilities=mod(prob(st.size)))
+
+
+def in_degrees(hmm):
+    """In-degree of every state over distinct (source, destination) pairs (duplicates count once)."""
+    n = int(hmm.states_num)
+    pairs = np.unique(hmm.trans_cols.astype(np.int64) * n + hmm.trans_rows.astype(np.int64))
+    return np.bincount(pairs // n, minlength=n)
+
+
+# The fused planner's rules (runtime.cpp make_plan), restated: families (R, HM, XM, uniform heavy
+# rows) in the order they are tried, slot counts, workgroup cap and the LDS a geometry needs.
+FUSED_FAMILIES = ((2, 2, 2, True), (2, 2, 2, False), (4, 4, 4, False), (8, 4, 4, False), (16, 4, 4, False))
+FUSED_SLOTS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16)
+FUSED_MAX_THREADS = 512
+FUSED_MAX_LDS = 160 * 1024
+GENERIC_MAX_THREADS = 1024
+
+
+def fused_lds_bytes(sm, B, vstride):
+    ndma = (sm + 3) // 4
+    return (3 * vstride + 3 * ndma * B * 4) * 4 + 3 * 4 * 8 + 2 * 16 * 4 + 4096 + 64 + 16
+
+
+def _uniform_heavy(hmm, heavy, XM):
+    """analyse_uniform: every heavy row is one dominant weight over a light source set shared by all
+    heavy rows plus at most XM other terms."""
+    if not heavy:
+        return False
+    rows, cols = hmm.trans_rows.astype(np.int64), hmm.trans_cols.astype(np.int64)
+    _, first = np.unique(cols * int(hmm.states_num) + rows, return_index=True)
+    rows, cols, vals = rows[first], cols[first], hmm.trans_probs[first]
+    hset = set(heavy)
+    shared = None
+    for h in heavy:
+        sel = cols == h
+        k, w = rows[sel], vals[sel].view(np.uint32)
+        lightsrc = np.array([x not in hset for x in k], bool)
+        u = np.zeros(0, np.int64)
+        if lightsrc.any():
+            bits, cnt = np.unique(w[lightsrc], return_counts=True)
+            u = np.sort(k[lightsrc & (w == bits[np.argmax(cnt)])])  # first maximum: the lowest weight bits
+        if k.size - u.size > XM:
+            return False
+        if shared is None:
+            shared = u
+        elif not np.array_equal(u, shared):
+            return False
+    return True
+
+
+def expected_plan(hmm, max_threads=0, allow_uniform=True):
+    """What svh_model_info must report for this model's step kernel: dict(fused, family, slots,
+    threads, light_terms, heavy_rows, heavy_uniform); family -1 / slots 0: the generic kernel."""
+    n = int(hmm.states_num)
+    deg = in_degrees(hmm)
+    cap = min(max_threads, FUSED_MAX_THREADS) if max_threads > 0 else FUSED_MAX_THREADS
+    generic = dict(fused=False, family=-1, slots=0, threads=min(GENERIC_MAX_THREADS, (n + 63) // 64 * 64),
+                   light_terms=0, heavy_rows=0, heavy_uniform=0)
+    for fam, (R, HM, XM, uniform) in enumerate(FUSED_FAMILIES):
+        if uniform and not allow_uniform:
+            continue
+        heavy = [int(j) for j in np.nonzero(deg > R)[0]]
+        if len(heavy) > HM:
+            continue
+        if uniform and not _uniform_heavy(hmm, heavy, XM):
+            continue
+        for sm in FUSED_SLOTS:
+            B = max(64, ((n + sm - 1) // sm + 63) // 64 * 64)
+            if B > cap:
+                continue
+            vstride = (sm * B + 1 + 4 + 3) // 4 * 4
+            if fused_lds_bytes(sm, B, vstride) > FUSED_MAX_LDS:
+                continue
+            return dict(fused=True, family=fam, slots=sm, threads=B, light_terms=R, heavy_rows=len(heavy),
+                        heavy_uniform=int(uniform))
+        return generic
+    return generic

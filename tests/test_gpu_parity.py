@@ -123,16 +123,22 @@ def test_workgroup_geometries(threads):
 
 
 @pytest.mark.parametrize("n,degree,dense,seed", [
-    (900, 3, (), 1),          # chmm_gen.py shape: in-degree ~Poisson(3) -> R4/R8/R16 families
-    (257, 2, (5,), 2),        # one dense row -> general heavy rows
-    (300, 3, (0, 7, 299), 3),  # three dense rows -> R4+ families
-    (64, 1, (), 4),
+    (900, 3, (), 1),          # chmm_gen.py shape: in-degree ~Poisson(3), tail of 6..10 terms -> R8, 3 heavy rows
+    (257, 2, (5,), 2),        # one dense row -> R8 (the Poisson tail is too long for R2 / R4), 1 heavy row
+    (300, 3, (0, 7, 299), 3),  # three dense rows -> R8, 4 heavy rows (one from the tail)
+    (64, 1, (), 4),           # general R2, 2 heavy rows
     (1, 1, (), 5),            # single state
 ])
 def test_random_models(n, degree, dense, seed):
+    """chmm_gen.py-shaped models: all of them run the R8 family (general R2 for the two small ones)
+    at one or two slots -- asserted below; the other families, slot counts and heavy-row counts are
+    tests/test_fused_gpu.py's."""
     hmm = random_hmm(n, out_degree=degree, dense_rows=dense, seed=seed, zero_emis=0.05)
     seqs = random_seqs(20, [1, 2, 3, 17, 500], seed=seed)
-    check_against_oracle(hmm, seqs)
+    model = check_against_oracle(hmm, seqs)
+    info = model.info()
+    want = {900: (3, 2, 3), 257: (3, 1, 1), 300: (3, 1, 4), 64: (1, 1, 2), 1: (1, 1, 0)}[n]
+    assert info["kernel"] == _lib.SVH_KERNEL_FUSED and (info["family"], info["slots"], info["heavy_rows"]) == want, info
     check_against_oracle(hmm, seqs, kernel=_lib.SVH_KERNEL_GENERIC)
 
 
