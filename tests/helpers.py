@@ -311,3 +311,103 @@ def expected_plan(hmm, max_threads=0, allow_uniform=True):
                         heavy_uniform=int(uniform))
         return generic
     return generic
+
+
+# The dense `_spec` products and their run, restated from the definition in oracle/viterbi_oracle.h
+# with dense numpy arrays only (no CSR, no term lists): an implementation independent of both the
+# oracle's C and the device kernels.  Every add is one float32 add; +inf stands for "no term", and
+# fl(+inf + x) = +inf never wins a minimum, so minimising over every index equals minimising over
+# the stored terms (no score is -inf or NaN).
+def _dense_model(hmm):
+    """(E [S, n], T^T [n, n], start [n]) in float32: T^T[j][k] is the weight of k -> j, the first
+    tuple of a duplicate (k, j) wins; absent entries are +inf."""
+    n, S = int(hmm.states_num), int(hmm.emit_num)
+    E = np.asarray(hmm.emissions, np.float32).reshape(S, n)
+    tt = np.full((n, n), np.inf, np.float32)
+    dst, src = hmm.trans_cols.astype(np.int64), hmm.trans_rows.astype(np.int64)
+    _, first = np.unique(dst * n + src, return_index=True)  # the first occurrence of every (k, j)
+    tt[dst[first], src[first]] = np.asarray(hmm.trans_probs, np.float32)[first]
+    start = np.full(n, np.inf, np.float32)
+    cols = hmm.start_probabilities_cols.astype(np.int64)
+    _, first = np.unique(cols, return_index=True)
+    start[cols[first]] = np.asarray(hmm.start_probabilities, np.float32)[first]
+    return E, tt, start
+
+
+def _minplus(A, B):
+    """C[j][m] = min_p fl(A[j][p] + B[p][m]) in float32 (B may be a vector)."""
+    A, B = np.asarray(A, np.float32), np.asarray(B, np.float32)
+    if B.ndim == 1:
+        return (A + B[None, :]).min(axis=1)
+    out = np.empty((A.shape[0], B.shape[1]), np.float32)
+    for j in range(A.shape[0]):  # row by row: n^2 floats live, not n^3
+        out[j] = (A[j][:, None] + B).min(axis=0)
+    return out
+
+
+def spec_products_numpy(hmm, level):
+    """Dense level-`level` products [S^level, n, n] float32: M_o[j][k] = fl(E[o][j] + T^T[j][k]),
+    H[(k..., i)] = M_i (x) H[(k...)]; keys base S, the first symbol most significant."""
+    assert level >= 1
+    S = int(hmm.emit_num)
+    E, tt, _ = _dense_model(hmm)
+    M = E[:, :, None] + tt[None, :, :]
+    H = M
+    for _ in range(1, level):
+        H = np.stack([_minplus(M[i], H[k]) for k in range(H.shape[0]) for i in range(S)])
+    return H
+
+
+def spec_run_numpy(hmm, level, seq, products):
+    """Final scores [n] of one sequence at `_spec` level `level` (<= 1: every observation is a tail
+    step): v0 = fl(E[s0] + start), one product per `level` observations while that many remain,
+    then v' = M_o (x) v per observation."""
+    S = int(hmm.emit_num)
+    E, tt, start = _dense_model(hmm)
+    seq = [int(o) for o in seq]
+    v = E[seq[0]] + start
+    i = 1
+    if level > 1:
+        assert products.shape[0] == S ** level
+        while len(seq) - i >= level:
+            key = 0
+            for o in seq[i:i + level]:
+                key = key * S + o
+            v = _minplus(products[key], v)
+            i += level
+    for o in seq[i:]:
+        v = _minplus(E[o][:, None] + tt, v)
+    return v
+
+
+def spec_chunk_keys(seq, S, level):
+    """The product keys the chunks of one sequence use, in order."""
+    nch = (len(seq) - 1) // level
+    d = np.asarray(seq[1:1 + nch * level], np.int64).reshape(nch, level)
+    return d @ (S ** np.arange(level - 1, -1, -1, dtype=np.int64))
+
+
+def key_cover_seqs(S, level, tail_lens, seed):
+    """A ragged batch of len(tail_lens) sequences whose chunks use every one of the S^level keys
+    (each once, in a random order, dealt out in random uneven shares of at least one chunk; where
+    there are fewer keys than sequences some keys repeat).  Sequence r = a first observation, its
+    chunks, and a tail of tail_lens[r] observations (0 .. level - 1)."""
+    rng = np.random.default_rng(seed)
+    R = len(tail_lens)
+    assert R >= 1 and all(0 <= t < max(level, 1) for t in tail_lens)
+    nk = S ** level
+    keys = rng.permutation(nk)
+    if nk < R:
+        keys = np.concatenate([keys, rng.integers(0, nk, size=R - nk)])
+    cuts = np.sort(rng.choice(np.arange(1, keys.size), size=R - 1, replace=False)) if R > 1 else []
+    digits = (keys[:, None] // (S ** np.arange(level - 1, -1, -1, dtype=np.int64))[None, :]) % S
+    seqs = []
+    for part, tail in zip(np.split(digits, cuts), tail_lens):
+        seqs.append(np.concatenate([rng.integers(0, S, size=1), part.ravel(), rng.integers(0, S, size=int(tail))])
+                    .astype(np.uint64))
+    return seqs
+
+
+def covered_keys(seqs, S, level):
+    """Sorted distinct keys the chunks of a batch use."""
+    return np.unique(np.concatenate([spec_chunk_keys(s, S, level) for s in seqs]))
