@@ -161,7 +161,13 @@ typedef struct {
                               ranges of 128 diagonals, for batches that would put more than one wave on a
                               SIMD; at level >= 2 the tail's launch), 0 = the batch does not run that plan.
                               The environment variable SVH_DIAG_SM = 1 / 2, read when a model is created,
-                              forces either for every scores launch of that model (appended in ABI 4) */
+                              forces either for every scores launch of that model (appended in ABI 4).
+                              A scores launch that puts at most one workgroup on a CU runs one wave more per
+                              workgroup than svh_batch_plan's `threads` says: a loader wave, which refills the
+                              table ring and builds the step waves' streams (`threads` stays 64 x the sequences
+                              of a workgroup; lds_bytes includes its third stream buffer).  The environment
+                              variable SVH_DIAG_LOADER = 0 / 1, read when a model is created, forces the
+                              launches without / with it */
 } svh_model_info;
 /* The model's plan for a one-sequence scores-only run (kernel/threads/slots describe it). */
 int svh_model_get_info(svh_model_t m, svh_model_info* info);
@@ -216,8 +222,12 @@ int svh_batch_elapsed_ms(svh_batch_t b, float* ms);
  * of the batch's pipelined latency pass with every boundary exchange removed -- each wave sweeps
  * its block as the first block does, with no input from its neighbours and no waits -- so the
  * launch takes the step's own per-observation time plus the prologue.  Its scores go to a scratch
- * buffer (they are not the batch's results, which this call leaves untouched).  SVH_E_UNSUPPORTED
- * unless the batch's scores-only plan is the pipelined latency plan at its default table mode.
+ * buffer (they are not the batch's results, which this call leaves untouched).  For a batch whose
+ * scores-only plan is the diagonal plan (SVH_KERNEL_DIAG), which has no exchange, it is that plan's
+ * floor (batches of at least four sequences): its loader-wave launch with the loader wave idle, no
+ * LDS read in the full blocks' steps and without the partials, the arrival count, the combine and
+ * the re-run, i.e. the prologue and the steps' arithmetic alone.  SVH_E_UNSUPPORTED unless the
+ * batch's scores-only plan is one of the two (the latency plan at its default table mode).
  * Synchronous. */
 int svh_batch_step_floor_ms(svh_batch_t b, void* stream, uint32_t reps, float* ms);
 /* The plan svh_batch_run(level) launches for this batch (its sequence count and paths flag

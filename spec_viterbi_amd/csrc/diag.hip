@@ -105,6 +105,16 @@ constexpr uint32_t kDMaxSym = 32;
 #ifndef SVH_DIAG_CMPX2
 #define SVH_DIAG_CMPX2 1
 #endif
+// SVH_DIAG_LDPRIO (A/B of the loader-wave variant): the step waves' s_setprio level, 0 = none (as
+// measured: raising them costs 3 % at 50 sequences and nothing at 13)
+#ifndef SVH_DIAG_LDPRIO
+#define SVH_DIAG_LDPRIO 0
+#endif
+// SVH_DIAG_LDDRAIN (A/B of the loader-wave variant): 1 = the step waves wait for their LDS reads
+// (lgkmcnt(0)) ahead of the block's barrier as the plain variant does, 0 = they do not
+#ifndef SVH_DIAG_LDDRAIN
+#define SVH_DIAG_LDDRAIN 1
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif
@@ -142,10 +152,11 @@ __device__ __forceinline__ void exec_collect(uint64_t& alive) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1) {
+__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1, bool ld = false) {
     // ring [S][kDRS] float2 (dm = 2: [S][2][kDRS2] floats) | symbol template [S][8] | constants [W][2][kDK][kDE] |
     // ring addresses [W][2][kDK] | X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
-    return ((size_t)S * (dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * 2 * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
+    // (ld, the loader-wave variant: three stream buffers instead of two)
+    return ((size_t)S * (dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * (ld ? 3 : 2) * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
 }
 
 // Decoded paths (PATHS; the walk is pipe_paths.hip's diag entry): fold ring [W][kFS][64] floats behind
@@ -176,31 +187,54 @@ __host__ __device__ constexpr size_t diag_lds_paths(uint32_t W, uint32_t S, bool
 // read per plane yields {ea_a, ea_b} / {eb_a, eb_b} as register pairs and the chain and feeder
 // terms are one packed add each; the lanes of a block walk through four ring groups instead of
 // three, which the five groups still hold (group kb + 4 is written over group kb - 1).
-template <int W, bool SX, bool PATHS = false, int DM = 1>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
+//
+// LD (scores only): a loader wave.  The workgroup is W step waves and one wave more (wave W), which
+// does everything of a block that is not steps -- the ring refill of group kb + 4 for every symbol
+// plane and the three streams of all W sequences with their symbol loads -- and meets the step
+// waves at the one barrier per block; the step waves run block() / tail(), exec_collect and that
+// barrier only.  A stream built by another wave is ordered by the barrier alone, so the loader
+// builds block kb + 2 during block kb, into one of three buffers ("Loader wave").
+// After the last block the loader wave ends: the epilogue's barriers (and pipe_rerun_row's, written
+// for 64 W threads) then wait for the step waves only -- S_BARRIER: "If some waves in the
+// work-group have already terminated, this waits on only the surviving waves" (AMD Instinct CDNA3 /
+// CDNA4 ISA reference guides, SOPP instructions).
+template <int W, bool SX, bool PATHS = false, int DM = 1, bool LD = false, bool FL = false>
+__global__ __launch_bounds__(64 * (W + (LD ? 1 : 0))) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     static_assert(DM == 1 || (DM == 2 && !PATHS), "decoded paths keep one diagonal per lane");
+    static_assert(!LD || (!PATHS && SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0), "the loader wave: scores only");
+    static_assert(!FL || LD, "the floor is a loader-wave launch");
+    constexpr uint32_t NB = LD ? 3 : 2;                  // stream buffers per wave
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr uint32_t RW = 64 * DM;                     // diagonals (positions) per range
     constexpr uint32_t RS = DM == 2 ? kDRS2 : kDRS;      // pairs of floats per symbol in the ring
     const uint32_t S = m.S, NR = DM == 2 ? m.nrng2 : m.nrng, NP = NR * RW, P = m.P;
     float* ring = lds;                                   // [S][kDRS] {ea, eb}; DM = 2: [S][2][kDRS2]
     float* hcr = ring + (size_t)S * RS * 2;              // [S][8] stream template of symbol o
-    float* strm = hcr + S * 8;                           // [W][2][kDK] {A_F, A_S, X_FF, X_SS}
-    float* adr = strm + W * 2 * kDK * kDE;               // [W][2][kDK] ring address of (o_t, step)
-    float* xsf = adr + W * 2 * kDK;                      // [W][2][kDK] X_SF (SX only)
-    uint32_t* wnb = reinterpret_cast<uint32_t*>(xsf + (SX ? W * 2 * kDK : 0));  // [W] blocks of wave w
+    float* strm = hcr + S * 8;                           // [W][NB][kDK] {A_F, A_S, X_FF, X_SS}
+    float* adr = strm + W * NB * kDK * kDE;              // [W][NB][kDK] ring address of (o_t, step)
+    float* xsf = adr + W * NB * kDK;                     // [W][NB][kDK] X_SF (SX only)
+    uint32_t* wnb = reinterpret_cast<uint32_t*>(xsf + (SX ? W * NB * kDK : 0));  // [W] blocks of wave w
     uint32_t* rrow = wnb + W;                            // [W] row wave w's combine hands to the re-run
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t w = (uint32_t)uniform((int)(tid >> 6));
     const uint32_t rg = blockIdx.x % NR, grp = blockIdx.x / NR;
     const uint32_t q = grp * W + w;
-    const bool real = q < b.nseq;
+    const bool ldr = LD && w == W;                        // the loader wave (wave-uniform)
+    // FL (svh_batch_step_floor_ms, launched for m.dld == 3: timing only, wrong scores): the plan's
+    // floor -- the prologue and the steps' arithmetic alone.  The full blocks' steps issue no LDS
+    // read (every step takes the constants, the ring address and the pair the prologue read, as the
+    // SVH_DIAG_AB = 1 and 2 diagnostics do); the loader wave fills group 4 and the third stream
+    // buffer in the prologue (every LDS word a tail step reads is then a valid, if stale, entry) and
+    // only meets the barriers; the step waves store their scores and skip the partials, the arrival
+    // count, the combine and the re-run.
+    constexpr bool flr = FL;
+    const bool real = (!LD || w < W) && q < b.nseq;
     const uint32_t ring_a = lds_addr(ring);
 
     // stream template: {A_F, A_S, X_FF, X_SS, X_SF, LDS address of plane o, 0, 0}
-    for (uint32_t i = tid; i < S * 8; i += 64 * W) {
+    for (uint32_t i = tid; i < S * 8; i += 64 * (W + (LD ? 1 : 0))) {
         const uint32_t o = i >> 3, k = i & 7u;
         const float* h = m.hc + o * 8;  // A_S A_F X_SS X_FF | X_SF E_F E_S 0
         float v = 0.0f;
@@ -219,7 +253,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     const uint32_t first = beg ? beg : 1u;                // first observation the steps run (state at first-1)
     const uint32_t nst = len > first ? len - first : 0u;  // steps: observations first .. len-1
     const uint32_t nb = (nst + kDK - 1) / kDK;
-    if (lane == 0) {
+    if (lane == 0 && (!LD || w < W)) {
         wnb[w] = nb;
         rrow[w] = kNoRow;
     }
@@ -280,11 +314,118 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             if (SX) xsf[e] = h1.x;
         }
     };
+    // ---- the loader wave's own forms of the four (LD): the refill's chunks over its 64 lanes, the
+    // streams of every sequence u of the workgroup (three buffers: block kb's is kb % 3)
+    constexpr uint32_t kRepL = kCP * kDMaxSym / 64;
+    typedef float lvecl __attribute__((ext_vector_type(LD ? 4 * kRepL : 4)));
+    lvecl lregl = 0.0f;
+    const uint8_t* lsym[W] = {};
+    uint32_t llen[W] = {}, lfirst[W] = {}, lsymv[W] = {};
+    bool lreal[W] = {};
+    auto gloadl = [&](uint32_t g) {
+        if constexpr (LD) {
+            const uint32_t c0 = (rg * RW + g * kDK) % NP;
+#pragma unroll
+            for (uint32_t r = 0; r < kRepL; ++r) {
+                if (r * 64 < nchunk) {  // (wave-uniform)
+                    const uint32_t k = min(lane + r * 64, nchunk - 1);
+                    const float4 v = DM == 2 ? *reinterpret_cast<const float4*>(m.dtab2 + (size_t)(k / (kCP / 2)) * NP + c0 + 4 * (k % (kCP / 2)))
+                                             : *reinterpret_cast<const float4*>(m.dtab + (size_t)(k / kCP) * NP + c0 + 2 * (k % kCP));
+                    lregl[4 * r] = v.x;
+                    lregl[4 * r + 1] = v.y;
+                    lregl[4 * r + 2] = v.z;
+                    lregl[4 * r + 3] = v.w;
+                }
+            }
+        }
+    };
+    auto lwritel = [&](uint32_t g) {
+        if constexpr (LD) {
+            const uint32_t s0 = (g % kDG) * kDK;
+#pragma unroll
+            for (uint32_t r = 0; r < kRepL; ++r) {
+                const uint32_t k = lane + r * 64;
+                if (k < nchunk) {
+                    float* d = DM == 2 ? ring + (size_t)(k / (kCP / 2)) * kDRS2 + s0 + 4 * (k % (kCP / 2))
+                                       : ring + ((size_t)(k / kCP) * kDRS + s0 + 2 * (k % kCP)) * 2;
+                    const float4 v = make_float4(lregl[4 * r], lregl[4 * r + 1], lregl[4 * r + 2], lregl[4 * r + 3]);
+                    *reinterpret_cast<float4*>(d) = v;
+                    if (s0 < RW) *reinterpret_cast<float4*>(d + kDR * (DM == 2 ? 1 : 2)) = v;
+                }
+            }
+        }
+    };
+    auto symloadl = [&](uint32_t kb) {
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            const uint32_t t = lfirst[u] + kb * kDK + lane;
+            const uint32_t tc = t < llen[u] ? t : (llen[u] ? llen[u] - 1 : 0u);
+            lsymv[u] = (lreal[u] && lane < kDK) ? (uint32_t)lsym[u][tc] : 0u;
+        }
+    };
+    auto sbuildl = [&](uint32_t kb) {
+        if (lane < kDK) {
+            const uint32_t i = kb * kDK + 1 + lane;
+            const uint32_t ro = (i % kDR) * (DM == 2 ? 4u : 8u);
+            const uint32_t e0 = (kb % NB) * kDK + lane;
+#pragma unroll
+            for (int u = 0; u < W; ++u) {
+                const uint32_t o = lsymv[u] < S ? lsymv[u] : 0u;
+                const float4 h0 = *reinterpret_cast<const float4*>(hcr + o * 8);
+                const float2 h1 = *reinterpret_cast<const float2*>(hcr + o * 8 + 4);
+                const uint32_t e = u * NB * kDK + e0;
+                *reinterpret_cast<float4*>(strm + e * kDE) = h0;
+                adr[e] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + ro);
+                if (SX) xsf[e] = h1.x;
+            }
+        }
+    };
+    if constexpr (LD) {
+        if (ldr) {
+#pragma unroll
+            for (int u = 0; u < W; ++u) {
+                const uint32_t qu = grp * W + u;
+                lreal[u] = qu < b.nseq;
+                lsym[u] = b.symbols + (lreal[u] ? b.sym_off[qu] : 0);
+                llen[u] = lreal[u] ? (uint32_t)uniform((int)b.end[qu]) : 0u;
+                const uint32_t bu = lreal[u] ? (uint32_t)uniform((int)b.begin[qu]) : 0u;
+                lfirst[u] = bu ? bu : 1u;
+            }
+        }
+    }
 
     // ---- prologue: groups 0..3 in the ring, group 4 in flight; the stream of block 0
 #if SVH_DIAG_AB == 6  // diagnostics: the launch alone
     return;
 #endif
+    if constexpr (LD) {
+        // the step waves fill groups 0..3; the loader wave: group 4 in flight, the streams of blocks
+        // 0 and 1 (behind the barrier: they need the symbol template), the symbols of block 2
+        if (ldr) {
+            gloadl(4);
+            symloadl(0);
+        } else {
+            gload(0);
+            lwrite(0);
+            gload(1);
+            lwrite(1);
+            gload(2);
+            lwrite(2);
+            gload(3);
+            lwrite(3);
+        }
+        __syncthreads();  // the symbol template
+        if (ldr) {
+            sbuildl(0);
+            symloadl(1);
+            sbuildl(1);
+            symloadl(2);
+            if (flr) {
+                sbuildl(2);
+                lwritel(4);
+            }
+        }
+    } else {
 #if SVH_DIAG_AB != 4  // diagnostics: no prologue table loads (rows of one observation stay exact)
     gload(0);
     lwrite(0);
@@ -300,6 +441,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     __syncthreads();  // the symbol template
     sbuild(0);
     symload(1);
+    }
 
     // ---- decoded paths: this wave's record rows (lane-wise parts computed here, with every lane on)
     const uint32_t Lg = rg * 64 + lane;                   // the lane's diagonal: position (Lg + t) mod NP at observation t
@@ -370,7 +512,9 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     evec eq;
     // entry j of block kb in the streams' two buffers (j < 2 kDK: the next block's past kDK - 1): the
     // block's buffer or the other one (two bases per block, the rest is an immediate offset)
+    // (LD: three buffers, block kb's is kb % 3)
     auto spos = [&](uint32_t kb, uint32_t j) {
+        if constexpr (LD) return (w * NB + (j < kDK ? kb : kb + 1) % NB) * kDK + j % kDK;
         const uint32_t e0 = (w * 2 + (kb & 1u)) * kDK;
         return (j < kDK ? e0 : e0 ^ kDK) + j % kDK;
     };
@@ -540,9 +684,9 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         __builtin_amdgcn_sched_barrier(0);  // the block's work stays above the first check
 #pragma unroll
         for (uint32_t j = 0; j < kDK; ++j) {
-            const uint32_t a = SVH_DIAG_AB == 1 ? 0u : j % kNS, b2 = j % kNE;
+            const uint32_t a = (SVH_DIAG_AB == 1 || FL) ? 0u : j % kNS, b2 = FL ? 0u : j % kNE;
             const float4 h = make_float4(hq[4 * a], hq[4 * a + 1], hq[4 * a + 2], hq[4 * a + 3]);
-            const float xs = SX ? xq[SVH_DIAG_AB == 1 ? 0u : j % (2 * kAG)] : 0.0f;
+            const float xs = SX ? xq[(SVH_DIAG_AB == 1 || FL) ? 0u : j % (2 * kAG)] : 0.0f;
             const f2 e = DM == 2 ? (f2){eq[4 * b2], eq[4 * b2 + 1]} : (f2){eq[2 * b2], eq[2 * b2 + 1]};
             // at even steps, together: the constants of steps j + kPS and j + kPS + 1 (the next block's
             // past kDK - 1), then the ring pairs of steps j + kPE and j + kPE + 1, then, every kAG
@@ -554,19 +698,19 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             // places its own counted waits where this one does not suffice: the count is a matter
             // of speed only.
             if (j % 2 == 0) {
-                if (SVH_DIAG_AB != 1) {
+                if (SVH_DIAG_AB != 1 && !FL) {
                     sread(kb, j + kPS, (j + kPS) % kNS);
                     sread(kb, j + kPS + 1, (j + kPS + 1) % kNS);
                 }
-                if (SVH_DIAG_AB != 2) {
+                if (SVH_DIAG_AB != 2 && !FL) {
                     eread(j + kPE);
                     eread(j + kPE + 1);
                 }
-                if (SVH_DIAG_AB != 1 && j % kAG == 0) {
+                if (SVH_DIAG_AB != 1 && !FL && j % kAG == 0) {
                     gread(aq, adr, kb, j + 2 * kAG);
                     if (SX) gread(xq, xsf, kb, j + kAG);
                 }
-                if (SVH_DIAG_AB == 0) {
+                if (SVH_DIAG_AB == 0 && !FL) {
                     // lgkmcnt(5 or 6) alone (PATHS: and the two ring writes since the pairs' reads;
                     // DM = 2: the pairs of two steps are four reads)
                     __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0) + (DM == 2 ? 2 : 0)) << 8));
@@ -596,7 +740,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     };
     // the row's last, partial block: plain steps
     auto tail = [&](uint32_t kb, uint32_t rem) {
-        const uint32_t e0 = (w * 2 + (kb & 1u)) * kDK;
+        const uint32_t e0 = LD ? (w * NB + kb % NB) * kDK : (w * 2 + (kb & 1u)) * kDK;
         if constexpr (PATHS) {  // groups of kFS steps, each with its collect and fold
             for (uint32_t g0 = 0; g0 < rem; g0 += kFS) {
                 const uint32_t n = rem - g0 < kFS ? rem - g0 : kFS;
@@ -628,12 +772,32 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         exec_collect(alive);  // right behind the loop's scalar branch: no other branch sees a partial EXEC
     };
 
+    if constexpr (LD) {
+        if (ldr) {
+            // the loader wave: during block k the refill of group k + 4 (loaded one block earlier; into
+            // the slots of group k - 1, last read in block k - 1), the loads of group k + 5, the streams
+            // of block k + 2 (into the buffer of block k - 1) and the symbols of block k + 3; its LDS
+            // writes are complete (lgkmcnt(0)) when it arrives at the block's barrier
+            for (uint32_t k = 0; k < nbmax; ++k) {
+                if (!flr) {
+                    sbuildl(k + 2);
+                    symloadl(k + 3);
+                    lwritel(k + 4);
+                    gloadl(k + 5);
+                }
+                lds_barrier();
+            }
+            return;  // (ends here: see the note on S_BARRIER above the kernel)
+        }
+        // the step waves ahead of the loader wave that shares a SIMD with one of them
+        if (SVH_DIAG_LDPRIO) __builtin_amdgcn_s_setprio(SVH_DIAG_LDPRIO);
+    }
     for (uint32_t k = 0; k < nbmax; ++k) {
         const uint32_t rem = k < nb ? nst - k * kDK : 0u;
         const bool full = k < nb && rem >= kDK;
         // (issuing this work between the block's steps instead measured the same: 0.1940 against
         // 0.1934 ms; the per-block cost is the barrier and its LDS drain, profiles/r06_diag/)
-        blockwork(k);
+        if constexpr (!LD) blockwork(k);
         if (k < nb) {
 #ifdef SVH_DIAG_SIMPLE  // diagnostics: every block through the plain steps (no software pipeline)
             tail(k, rem >= kDK ? kDK : rem);
@@ -642,7 +806,12 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
             else tail(k, rem);
 #endif
         }
-        if (SVH_DIAG_AB != 3) lds_barrier();
+        // (LD, SVH_DIAG_LDDRAIN = 0: the bare barrier.  What a step wave has in flight here are the
+        // prefetches of the next block's first steps -- LDS returns in order, and every earlier read
+        // has been used -- into its stream buffer and ring groups, none of which the loader wave
+        // writes in the coming period: DESIGN.md 5l)
+        if (LD && !SVH_DIAG_LDDRAIN) asm volatile("s_barrier" ::: "memory");
+        else if (SVH_DIAG_AB != 3) lds_barrier();
     }
 
     if (DM == 2 && !SVH_DIAG_CMPX2) alive &= __builtin_amdgcn_ballot_w64(nviol == 0);
@@ -702,7 +871,7 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         wave_lexmin63(bv, bk);
         const float cmin = wave_min63(c);
         const bool any_viol = alive != ~0ull;
-        if (lane == 63) {
+        if (lane == 63 && !flr) {
             uint64_t* part = x.part + ((size_t)q * x.G + rg) * 2;
             g_st64(part, ((uint64_t)(any_viol ? 1u : 0u) << 32) | __builtin_bit_cast(uint32_t, cmin));
             g_st64(part + 1, lex_key(bv, bk));
@@ -805,10 +974,29 @@ const void* diag_ptr(bool sx) {
     return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, DM>)
               : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM>);
 }
+template <int W, int DM>
+const void* diag_loader_ptr(bool sx) {
+    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) {  // (diagnostic builds keep the plain variant: diag_loader_for)
+        return nullptr;
+    } else {
+        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, DM, true>)
+                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM, true>);
+    }
+}
 // (Only the instantiations without X_SF: with both PATHS and SX the block's body is past the
 // compiler's limit for `#pragma unroll`, the 64 steps are then unrolled in part, the register
 // vectors indexed at run time, and the kernel is some 600 instructions per step.  Models whose S
 // takes a term from F keep the chain path variant: diag_paths_fit.)
+// (the floor: workgroups of four sequences only)
+template <int DM>
+const void* diag_floor_ptr(bool sx) {
+    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) {
+        return nullptr;
+    } else {
+        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<4, true, false, DM, true, true>)
+                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<4, false, false, DM, true, true>);
+    }
+}
 template <int W>
 const void* diag_paths_ptr() {
     static_assert(kDK == 64, "the path records' block layout (two mask words, two checkpoints per block)");
@@ -819,14 +1007,14 @@ const void* diag_paths_ptr() {
 
 uint32_t diag_waves_for(uint64_t nseq) { return nseq >= 4 ? 4u : nseq >= 2 ? 2u : 1u; }
 
-static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1) {
+static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1, bool ld = false) {
     const size_t rerun = (2 * (size_t)P + 2 * W) * 4;  // pipe_rerun_row: v[2][P], red[2][W]
-    const size_t mainb = diag_lds_main(W, S, sx, dm);
+    const size_t mainb = diag_lds_main(W, S, sx, dm, ld);
     return mainb > rerun ? mainb : rerun;
 }
 
 // (the larger of the two kernels': models that use X_SF keep one stream more)
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm) { return diag_lds(W, S, P, true, dm); }
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm, bool ld) { return diag_lds(W, S, P, true, dm, ld); }
 
 uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
     if (paths || !m.dtab2 || !m.nrng2 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) return 1;
@@ -834,6 +1022,18 @@ uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths
     if (resumed || !m.cus) return 1;
     const uint64_t W = diag_waves_for(nseq);
     return (nseq + W - 1) / W * W * m.nrng > 4ull * m.cus ? 2 : 1;
+}
+
+bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
+    if (paths || !nseq || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || m.dld == 1) return false;  // (dld: kernels.h)
+    const uint32_t W = diag_waves_for(nseq);
+    const uint32_t dm = diag_sm_for(m, nseq, resumed, paths);
+    if (diag_lds(W, m.S, m.P, m.sx != 0, dm, true) > 160 * 1024) return false;
+    if (m.dld == 3) return W == 4;  // (the floor variant: svh_batch_step_floor_ms)
+    if (m.dld == 2) return true;
+    // a wave alone on its SIMD has no neighbour to hide the block's other work behind, and the third
+    // stream buffer costs no residency: launches of at most one workgroup per CU
+    return m.cus && (nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng) <= m.cus;
 }
 
 size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx) { return diag_lds_paths(W, S, sx); }
@@ -861,10 +1061,14 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     const uint32_t dm = diag_sm_for(m, b.nseq, b.v_in != nullptr, paths);
     if (dm == 2 && ((size_t)m.nrng2 * 128 != m.P || x.G < m.nrng2)) return hipErrorInvalidValue;
     const bool sx = m.sx != 0;
+    const bool ld = diag_loader_for(m, b.nseq, b.v_in != nullptr, paths);
     const void* fn = paths     ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
+                     : ld && m.dld == 3 ? (dm == 2 ? diag_floor_ptr<2>(sx) : diag_floor_ptr<1>(sx))
+                     : ld      ? (dm == 2 ? (W == 4 ? diag_loader_ptr<4, 2>(sx) : W == 2 ? diag_loader_ptr<2, 2>(sx) : diag_loader_ptr<1, 2>(sx))
+                                          : (W == 4 ? diag_loader_ptr<4, 1>(sx) : W == 2 ? diag_loader_ptr<2, 1>(sx) : diag_loader_ptr<1, 1>(sx)))
                      : dm == 2 ? (W == 4 ? diag_ptr<4, 2>(sx) : W == 2 ? diag_ptr<2, 2>(sx) : diag_ptr<1, 2>(sx))
                                : (W == 4 ? diag_ptr<4>(sx) : W == 2 ? diag_ptr<2>(sx) : diag_ptr<1>(sx));
-    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm);
+    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm, ld);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng);
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
@@ -886,7 +1090,7 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     FusedBatch bb = b;
     PipeScratch xx = x;
     void* args[] = {&mm, &bb, &xx};
-    const hipError_t e = hipLaunchKernel(fn, dim3((uint32_t)grid), dim3(64 * W), args, lds, stream);
+    const hipError_t e = hipLaunchKernel(fn, dim3((uint32_t)grid), dim3(64 * (W + (ld ? 1 : 0))), args, lds, stream);
 #if SVH_DIAG_FINISH
     if (e != hipSuccess) return e;
     const void* fin = m.sx ? reinterpret_cast<const void*>(&diag_finish_kernel<true>)

@@ -229,6 +229,10 @@ struct PipeModel {
     unsigned long long* stamps;  // diagnostics (SVH_PIPE_DEBUG): [ticket][W][8] counters, or null
     uint32_t diag;               // diagnostics with stamps (SVH_PIPE_DEBUG bits > 1): 1 = no boundary
                                  // exchange (every wave runs as block 0; timing only, wrong results)
+    uint32_t dld;                // diagonal plan (in the padding ahead of dtab2: the kernels' argument layout is
+                                 // unchanged), SVH_DIAG_LOADER at model creation: 1 = never, 2 = always the
+                                 // loader-wave variant, 0 = diag_loader_for's rule; 3 (svh_batch_step_floor_ms's
+                                 // copy of the model only) = the plan's floor (diag.hip FL): timing only
     // diagonal plan, two diagonals per lane (diag.hip DM = 2): the same table split into planes,
     // [S][2][128 nrng2] floats (ea plane, eb plane per symbol; 128 nrng2 = P), nrng2 ranges of 128
     // diagonals per sequence; null: one diagonal per lane only
@@ -314,13 +318,18 @@ inline size_t pipe_path_lds_bytes(uint32_t W) { return (size_t)W * 8 * kPQuadStr
 // A workgroup is diag_waves_for(nseq) sequences x one range; rows whose speculation fails are re-run
 // in the same launch.  A scores row starts at observation 0 or resumes at begin > 0 from v_in.
 uint32_t diag_waves_for(uint64_t nseq);
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1);
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1, bool ld = false);
 // Diagonals per lane of a scores launch (1 or 2).  Two -- ranges of 128 diagonals, half as many waves,
 // each paying the step's per-wave part once for 128 positions -- where one per lane would put more
 // than one wave on a SIMD: ceil(nseq / W) W nrng > 4 CUs.  Rows resumed from v_in (the _spec tail,
 // time-parallel segments) and path batches keep one.  PipeModel::dsm (SVH_DIAG_SM) forces either for
 // every scores launch.
 uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
+// The loader-wave variant of a scores launch (diag.hip LD): the workgroup runs one wave more, which
+// does the blocks' ring refill and stream build for the step waves.  Where a launch puts at most one
+// workgroup on a CU (a step wave is then alone on its SIMD); PipeModel::dld (SVH_DIAG_LOADER = 0 / 1)
+// forces either for every scores launch whose LDS fits.
+bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
 // Diagonal plan, decoded paths (diag.hip PATHS, pipe_paths.hip's diag walk).  Models whose F wins

@@ -839,6 +839,8 @@ void DevicePipePlan::upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream
             const int v = std::atoi(e);
             view.dsm = v == 1 || v == 2 ? (uint32_t)v : 0u;
         }
+        // SVH_DIAG_LOADER = 0 / 1: without / with the loader wave for every scores launch (tests, A/B)
+        if (const char* e = std::getenv("SVH_DIAG_LOADER"); e && *e) view.dld = std::atoi(e) ? 2u : 1u;
     }
     view.emax2 = p.emax2;
     // the pair-table step wherever it applies: TM = 4 (indexed operands, packed feeder terms:
@@ -1556,7 +1558,7 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
         i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
-        i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm);
+        i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm, diag_loader_for(pipe.view, nseq, false, false));
     } else if (!paths && level >= 2 && nseq && diag_for(nseq)) {  // the _spec tail's launch
         i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, true, false);
     }
@@ -2478,9 +2480,20 @@ float Batch::step_floor_ms(hipStream_t s, uint32_t reps) {
     DeviceGuard g(model->device);
     if (!s) s = model->stream;
     const DevicePipePlan* pp = model->pipe_for(nseq);
-    if (!pp || pp->plan.wide || pp->view.tm != 4 || pp->plan.W != 4 || !model->band_for(false, nseq))
-        throw Error(SVH_E_UNSUPPORTED, "step floor: the batch's plan is not the pipelined latency plan (TM 4)");
-    floor_scratch.ensure(nseq, pp->plan.G, s);
+    // a batch whose scores pass runs the diagonal plan: that plan's floor -- its loader-wave launch
+    // with the loader wave idle, no LDS reads in the steps and no partials, arrival count, combine or
+    // re-run (diag.hip FL, dld = 3), i.e. the prologue and the steps' arithmetic alone; every other
+    // batch: the latency plan's
+    const DevicePipePlan* dp = paths ? nullptr : model->diag_for(nseq);
+    PipeModel dview{};
+    if (dp) {
+        dview = dp->view;
+        dview.dld = 3;
+        if (!diag_loader_for(dview, nseq, false, false)) dp = nullptr;
+    }
+    if (!dp && (!pp || pp->plan.wide || pp->view.tm != 4 || pp->plan.W != 4 || !model->band_for(false, nseq)))
+        throw Error(SVH_E_UNSUPPORTED, "step floor: the batch's plan is neither the diagonal plan nor the pipelined latency plan (TM 4)");
+    floor_scratch.ensure(nseq, dp ? std::max(dp->plan.nrng, dp->plan.nrng2) : pp->plan.G, s);
     const size_t n = model->host.n;
     d_floor_out.reserve(16 + (size_t)nseq * n * 4);
     FusedBatch fb;
@@ -2496,13 +2509,16 @@ float Batch::step_floor_ms(hipStream_t s, uint32_t reps) {
     hip_check(hipEventCreate(&e0), "hipEventCreate");
     hip_check(hipEventCreate(&e1), "hipEventCreate");
     float ms = 0;
+    auto launch_floor = [&]() {
+        return dp ? launch_diag(dview, fb, floor_scratch.view, s) : launch_pipe(pp->view, fb, floor_scratch.view, s, true);
+    };
     try {
         floor_scratch.note_launch(s);
-        hip_check(launch_pipe(pp->view, fb, floor_scratch.view, s, true), "step-floor kernel (warm-up)");
+        hip_check(launch_floor(), "step-floor kernel (warm-up)");
         hip_check(hipEventRecord(e0, s), "hipEventRecord");
         for (uint32_t r = 0; r < reps; ++r) {
             floor_scratch.note_launch(s);
-            hip_check(launch_pipe(pp->view, fb, floor_scratch.view, s, true), "step-floor kernel");
+            hip_check(launch_floor(), "step-floor kernel");
         }
         hip_check(hipEventRecord(e1, s), "hipEventRecord");
         hip_check(hipEventSynchronize(e1), "hipEventSynchronize");

@@ -232,7 +232,8 @@ class DeviceBatch:
 
     def step_floor_ms(self, reps: int = 10, stream: int | None = None) -> float:
         """The latency plan's pass with every boundary exchange removed (svh_batch_step_floor_ms):
-        the step's own per-observation time, the roofline the exchange is measured against.  Leaves
+        the step's own per-observation time, the roofline the exchange is measured against; for a
+        batch on the diagonal plan, that plan's launch with the prologue and the steps' arithmetic alone.  Leaves
         the batch's results untouched."""
         ms = ctypes.c_float()
         _lib.check(_lib.lib.svh_batch_step_floor_ms(self._h, ctypes.c_void_p(stream or 0), int(reps), ctypes.byref(ms)))
