@@ -32,7 +32,8 @@ extern "C" {
 
 #define SVH_ABI_VERSION 4  /* 2: svh_model_info pipe_* fields, SVH_KERNEL_PIPE, svh_batch_fallbacks;
                               3: pipe_max_nseq_paths, SVH_KERNEL_SPEC2_PIPE, SVH_BATCH_NO_TIMING;
-                              4: SVH_KERNEL_DIAG, svh_model_info diag_* fields */
+                              4: SVH_KERNEL_DIAG, svh_model_info diag_* fields (SVH_KERNEL_SPEC2_DIAG
+                                 was appended to the kernel ids without an ABI change) */
 
 enum {
     SVH_OK = 0,
@@ -74,7 +75,7 @@ void svh_ess_free(svh_ess_t e);
  * the fused (or generic) kernel with 16-bit backpointers. */
 enum { SVH_KERNEL_AUTO = 0, SVH_KERNEL_FUSED = 1, SVH_KERNEL_GENERIC = 2, SVH_KERNEL_BAND = 3,
        SVH_KERNEL_CHAIN = 4, SVH_KERNEL_PIPE = 5, SVH_KERNEL_PIPE_WIDE = 6, SVH_KERNEL_SPEC2 = 7,
-       SVH_KERNEL_SPEC2_PIPE = 8, SVH_KERNEL_DIAG = 9 };
+       SVH_KERNEL_SPEC2_PIPE = 8, SVH_KERNEL_DIAG = 9, SVH_KERNEL_SPEC2_DIAG = 10 };
 /* PIPE: the pipelined chain kernel (MSV-shaped models whose feeder row N takes terms only from
  * the light rows and itself): a sequence's states are split over many waves and CUs; N's light
  * term is speculated away and checked exactly at every observation, and a sequence that fails
@@ -102,7 +103,16 @@ enum { SVH_KERNEL_AUTO = 0, SVH_KERNEL_FUSED = 1, SVH_KERNEL_GENERIC = 2, SVH_KE
  * per-observation light minima, and a traceback kernel walks them (pipe_paths.hip); rows whose
  * speculation fails run on the chain kernel's path variant (svh_batch_fallbacks).  Other models
  * decode their paths on the chain kernel, and svh_batch_plan says so.  AUTO's path batches keep
- * the pipelined plan. */
+ * the pipelined plan.
+ * SPEC2_DIAG (reported by svh_batch_plan only, svh_model_create rejects it): _spec level 2 on the
+ * diagonal plan (diag_l2.hip) for models created with DIAG: every chunk of two observations of every
+ * row in one launch, a lane advancing two states per chunk so that its chain input is again its own
+ * score; the light term of N and its two-hop terms are speculated away and checked exactly as on
+ * SPEC2_PIPE, and flagged rows are re-run by spec2.hip with identical results.  Taken when the
+ * on-chip level-2 plan exists (it re-runs the flagged rows), every score is >= 0, the model has at
+ * most 32 symbols, its sink row takes no term from N, and two workgroups fit a CU's LDS.  A DIAG
+ * model that does not qualify runs its level-2 chunks on spec2.hip (SPEC2), one workgroup per
+ * sequence; its _spec tail runs on the diagonal plan either way. */
 
 typedef struct {
     int32_t device;      /* HIP device ordinal; -1 = the caller's current device */
@@ -233,13 +243,14 @@ int svh_batch_step_floor_ms(svh_batch_t b, void* stream, uint32_t reps, float* m
 /* The plan svh_batch_run(level) launches for this batch (its sequence count and paths flag
  * decide between the narrow and the wide chain plan): kernel/threads/slots of the model info. */
 int svh_batch_plan(svh_batch_t b, uint32_t level, svh_model_info* info);
-/* Rows of the last run whose pipelined pass (SVH_KERNEL_PIPE, _PIPE_WIDE, _SPEC2_PIPE) failed its
+/* Rows of the last run whose pipelined pass (SVH_KERNEL_PIPE, _PIPE_WIDE, _SPEC2_PIPE, _SPEC2_DIAG) failed its
  * speculation check and were re-run exactly (in the same launch, by the serial chain kernel, or at
  * level 2 by the on-chip chunk kernel; results are identical either way); 0 if the last run did
  * not use a pipelined kernel.  Waits for the run. */
 int svh_batch_fallbacks(svh_batch_t b, uint64_t* rows);
 /* The same per row: flags[q] (nseq words) bit 0 = the step pass re-ran row q, bit 1 = the _spec
- * level-2 pass on the pipelined plan handed it to the on-chip chunk kernel.  Waits for the run. */
+ * level-2 pass on the pipelined plan (SVH_KERNEL_SPEC2_PIPE) or on the diagonal plan
+ * (SVH_KERNEL_SPEC2_DIAG) handed it to the on-chip chunk kernel.  Waits for the run. */
 int svh_batch_fallback_rows(svh_batch_t b, uint32_t* flags);
 /* Whether this build holds the pipelined latency kernel at `slots` x `waves` with step table mode
  * `table_mode` (pipe_kernel.h TM; SVH_PIPE_SM / SVH_PIPE_WAVES / SVH_PIPE_TM select them).  The

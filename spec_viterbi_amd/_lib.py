@@ -35,6 +35,7 @@ SVH_KERNEL_PIPE_WIDE = 6
 SVH_KERNEL_SPEC2 = 7  # svh_batch_plan only: _spec level 2 on chip
 SVH_KERNEL_SPEC2_PIPE = 8  # svh_batch_plan only: _spec level 2 on the pipelined latency plan
 SVH_KERNEL_DIAG = 9  # the diagonal plan (diag.hip): scores-only passes, no inter-wave exchange
+SVH_KERNEL_SPEC2_DIAG = 10  # svh_batch_plan only: _spec level 2 on the diagonal plan (diag_l2.hip)
 SVH_BATCH_PATHS = 1
 SVH_BATCH_NO_TIMING = 2  # no start/stop events per run (svh_batch_elapsed_ms unavailable)
 SVH_MODEL_SPEC_DENSE = 1

@@ -332,6 +332,16 @@ uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths
 bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
+// _spec level 2 on the diagonal plan (diag_l2.hip): every chunk of two observations of every row in
+// one launch -- a lane advances two positions per chunk, so its chain input is again its own score.
+// Row q starts from the first observation's state in b.v_in (row q) and ends in b.scores (row q;
+// rows of 0 chunks are copied through); rows whose speculation fails are flagged in x.viol (re-run
+// by spec2_kernel, runtime.cpp).  Workgroups of diag_waves_for(nseq) sequences x one range.  Models
+// whose S takes a term from F (sx), with a negative score (emax2 = +inf), more than 32 symbols or an
+// LDS footprint that keeps two workgroups off a CU are not supported.
+bool diag_l2_supported(const PipeModel& m);
+size_t diag_l2_lds_bytes(uint32_t W, uint32_t S);
+hipError_t launch_diag_l2(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
 // Diagonal plan, decoded paths (diag.hip PATHS, pipe_paths.hip's diag walk).  Models whose F wins
 // every tie (PipeModel::ties_heavy) and whose S takes no term from F (sx == 0).  Rows whose speculation fails are flagged in x.viol and left to
 // the chain kernel's path variant, as on the pipelined plan.  Per sequence of length len, with

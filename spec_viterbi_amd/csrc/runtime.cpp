@@ -1248,6 +1248,10 @@ bool Model::pipe_l2_on() const {
            (kernel_pref == SVH_KERNEL_AUTO || kernel_pref == SVH_KERNEL_PIPE);
 }
 
+bool Model::diag_l2_on() const {
+    return kernel_pref == SVH_KERNEL_DIAG && spec2_on && pipe.plan.ok && diag_l2_supported(pipe.view);
+}
+
 const DevicePlan* Model::plan_for(bool paths) const {
     if (kernel_pref == SVH_KERNEL_GENERIC) return nullptr;
     const DevicePlan* p = paths ? paths_plan : &fast_plan;
@@ -1579,6 +1583,13 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         i.threads = (int32_t)(64 * pipe.plan.W);
         i.slots = (int32_t)pipe.plan.SM;
         i.lds_bytes = pipe_lds_bytes(pipe.plan.W, host.S);
+        i.spec_bytes = 0;
+    } else if (level == 2 && spec_level == 2 && nseq && diag_l2_on()) {  // the chunks on the diagonal plan
+        const uint32_t w = diag_waves_for(nseq);
+        i.kernel = SVH_KERNEL_SPEC2_DIAG;
+        i.threads = (int32_t)(64 * w);
+        i.slots = 1;
+        i.lds_bytes = diag_l2_lds_bytes(w, host.S);
         i.spec_bytes = 0;
     } else if (level == 2 && spec_level == 2 && spec2_on && nseq) {  // the chunks run on chip (spec2.hip)
         const Spec2Plan& sp = spec2.plan;
@@ -1986,8 +1997,12 @@ void Batch::run(uint32_t level, hipStream_t s) {
         // level 2 on the pipelined latency plan (pipe_l2.hip): every chunk of every row in one
         // launch into the second half of vbuf; rows whose speculation fails run again on spec2_kernel
         // from the first step's state (first half) into the second half; the tail reads row nseq + q
-        const bool l2pipe = on_chip && model->pipe_l2_on();
-        const uint32_t ready = level | (on_chip ? 0x100u : 0u) | (l2pipe ? 0x200u : 0u);
+        const bool l2pipe_on = on_chip && model->pipe_l2_on();
+        // level 2 on the diagonal plan (diag_l2.hip), models created with SVH_KERNEL_DIAG: the same
+        // buffers and the same re-run of flagged rows, the chunks' launch reads the first step's row q
+        const bool l2diag = on_chip && !l2pipe_on && model->diag_l2_on();
+        const bool l2pipe = l2pipe_on || l2diag;  // (either: the chunks end in the second half, flags in d_l2viol)
+        const uint32_t ready = level | (on_chip ? 0x100u : 0u) | (l2pipe_on ? 0x200u : 0u) | (l2diag ? 0x400u : 0u);
         if (spec_ready_level != ready) {
             std::vector<uint32_t> nch(nseq), tb(nseq), vrow(nseq);
             for (uint32_t q = 0; q < nseq; ++q) {
@@ -2007,7 +2022,19 @@ void Batch::run(uint32_t level, hipStream_t s) {
         }
         float* vb = d_vbuf.as<float>();
         hip_check(launch_first_step(csr, fb.symbols, fb.sym_off, nseq, vb, s), "spec first step");
-        if (l2pipe) {
+        if (l2diag) {
+            const DevicePipePlan& pl = model->pipe;
+            pipe.ensure(nseq, pl.plan.nrng, s);
+            PipeScratch x2 = pipe.view;
+            x2.viol = d_l2viol.as<uint32_t>();  // its own flags: the tail's pass rewrites pipe.view.viol
+            FusedBatch lb = fb;
+            lb.v_in = vb;
+            lb.scores = vb + (size_t)nseq * n;
+            lb.best = nullptr;
+            lb.pipe = nullptr;
+            hip_check(launch_diag_l2(pl.view, lb, x2, s), "diagonal level-2 kernel");
+            l2_ran = true;
+        } else if (l2pipe) {
             const DevicePipePlan& pl = model->pipe;
             pipe.ensure(nseq, pl.plan.G, s);
             pipe.note_launch(s);

@@ -253,6 +253,10 @@ struct Model {
     // level 2 runs on the pipelined latency plan (pipe_l2.hip) with spec2_kernel as its exact
     // fallback: the model has both, every score >= 0, and the kernel preference allows the pipe
     bool pipe_l2_on() const;
+    // level 2 runs on the diagonal plan (diag_l2.hip) with spec2_kernel as its exact fallback: the
+    // model was created with SVH_KERNEL_DIAG and has the on-chip plan and the diagonal table, every
+    // score is >= 0, at most 32 symbols, S takes no term from F and two workgroups fit a CU's LDS
+    bool diag_l2_on() const;
     bool spec_dense = false;  // svh_model_opts.flags & SVH_MODEL_SPEC_DENSE
 
     Model(const HostModel& h, const svh_model_opts* opts);
@@ -316,7 +320,7 @@ struct Batch {
 
     // _spec runs
     DeviceBuffer d_vbuf, d_nchunks, d_tbegin, d_vrow;
-    DeviceBuffer d_l2viol;  // level 2 on the pipelined plan: rows whose speculation failed (spec2 re-runs them)
+    DeviceBuffer d_l2viol;  // level 2 on the pipelined or the diagonal plan: rows whose speculation failed (spec2 re-runs them)
     bool l2_ran = false;    // the last run used it
     uint32_t spec_ready_level = 0;
     uint32_t max_chunks = 0;

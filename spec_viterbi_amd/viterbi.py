@@ -206,21 +206,25 @@ class DeviceBatch:
 
     def plan(self, level: int = 0) -> dict:
         """The plan run(level) launches for this batch (svh_batch_plan): model info fields with
-        kernel / threads / slots of the narrow or wide chain plan this batch selects."""
+        kernel / threads / slots of the narrow or wide chain plan this batch selects.  At level 2 a
+        model created with SVH_KERNEL_DIAG reports SVH_KERNEL_SPEC2_DIAG where its chunks run on the
+        diagonal plan (threads = 64 x sequences per workgroup, slots = 1, spec_bytes = 0)."""
         i = _lib.svh_model_info()
         _lib.check(_lib.lib.svh_batch_plan(self._h, int(level), ctypes.byref(i)))
         return {name: getattr(i, name) for name, _ in i._fields_}
 
     def fallbacks(self) -> int:
         """Rows of the last run that the pipelined kernel re-ran on the serial chain kernel
-        (svh_batch_fallbacks; 0 if the last run did not use the pipelined kernel)."""
+        (svh_batch_fallbacks; 0 if the last run did not use the pipelined kernel), rows of a level-2
+        pass on the pipelined or the diagonal plan that the on-chip chunk kernel re-ran included."""
         r = ctypes.c_uint64()
         _lib.check(_lib.lib.svh_batch_fallbacks(self._h, ctypes.byref(r)))
         return int(r.value)
 
     def fallback_rows(self) -> np.ndarray:
         """Per row (svh_batch_fallback_rows): bit 0 the step pass re-ran it exactly, bit 1 the
-        level-2 pipelined pass handed it to the on-chip chunk kernel."""
+        level-2 pass on the pipelined plan (SVH_KERNEL_SPEC2_PIPE) or on the diagonal plan
+        (SVH_KERNEL_SPEC2_DIAG) handed it to the on-chip chunk kernel."""
         f = np.zeros(self.nseq, np.uint32)
         _lib.check(_lib.lib.svh_batch_fallback_rows(self._h, _p(f, _u32)))
         return f
