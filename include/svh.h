@@ -12,6 +12,9 @@
  *                                   (batched: one call = many sequences)
  *   svh_spec_build                  Viterbi_spec_impl::spec_with    Viterbi_impl/Viterbi_spec_impl.h:11
  *   svh_viterbi(level >= 1)         Viterbi_spec_impl::run_Viterbi_spec  Viterbi_spec_impl.h:13-14
+ *   svh_batchset_*                  the harness's sweep of every model over one dataset
+ *                                   (benchmark/bench_Viterbi.h:37-59): one batch of sequences scored
+ *                                   against many models, the diagonal-plan members in one launch
  *
  * Conventions: plain pointers and sizes, no C++ or torch types; every call returns an int status
  * (SVH_OK == 0); svh_last_error() gives a thread-local message for the last failure; host
@@ -266,6 +269,48 @@ int svh_batch_debug_fault(svh_batch_t b, void* stream);
 /* Batch from uint8 symbols (the device format; e.g. straight from svh_reader_next). */
 int svh_batch_create_u8(svh_model_t m, uint64_t nseq, const uint64_t* offsets,
                         const uint8_t* symbols, uint32_t flags, svh_batch_t* out);
+
+/* ---- model sets: one batch of sequences scored against many models ---------------------- */
+/* The reference harness's workload is a sweep -- every .chmm against every dataset
+ * (benchmark/bench_Viterbi.h:37-59) -- and a cell of it is far too small for the chip: one model's
+ * launch is a few workgroups whose time is set by the sequence's serial steps.  A set holds one batch
+ * per model, all built from ONE symbol array, and svh_batchset_run scores them together: every
+ * member whose own scores plan for this batch is the diagonal plan (svh_batch_plan(level 0).kernel ==
+ * SVH_KERNEL_DIAG), whose sink row takes no term from the feeder row and whose alphabet has at most
+ * 32 symbols is GROUPED -- all grouped members run in one launch, each workgroup finding its member
+ * from its block index; every other member (general models, batches too wide for the
+ * diagonal plan, models created with another SVH_KERNEL_*) then runs its own svh_batch_run on the
+ * same stream.  Results are those of the members' stand-alone runs, bit for bit.
+ * Scope: scores only, levels 0 and 1 (identical).  svh_batchset_run(level >= 2) and
+ * svh_batchset_create with SVH_BATCH_PATHS return SVH_E_UNSUPPORTED: decoded paths and _spec
+ * level >= 2 run per batch (svh_batch_*).  Flags: SVH_BATCH_NO_TIMING only.
+ * Every model must be on one device (SVH_E_INVALID otherwise); a symbol out of range for any
+ * member's alphabet is SVH_E_RANGE at create.  The models must outlive the set.
+ * These entry points were appended without a change of SVH_ABI_VERSION (nothing that existed
+ * changed its layout or meaning; svh_batchset_create is absent from older libraries). */
+typedef struct svh_batchset* svh_batchset_t;
+typedef struct {
+    uint64_t members;    /* batches of the set (one per model) */
+    uint64_t grouped;    /* ... of which run in the set's one launch */
+    uint64_t launches;   /* of the last svh_batchset_run: the set launch (if any member is grouped) plus one
+                            svh_batch_run per member outside it; 0 before the first run */
+    uint64_t grid;       /* workgroups of the set launch */
+    uint64_t lds_bytes;  /* its LDS per workgroup: the largest of the grouped members' own footprints */
+    int32_t waves;       /* its sequences (waves) per workgroup: 1, 2 or 4, by the batch's sequence count */
+} svh_batchset_info;
+int svh_batchset_create(const svh_model_t* models, uint64_t nmodels, uint64_t nseq,
+                        const uint64_t* offsets, const uint8_t* symbols, uint32_t flags, svh_batchset_t* out);
+/* Enqueue one pass of every member on `stream` (NULL: the first model's stream); asynchronous. */
+int svh_batchset_run(svh_batchset_t s, uint32_t level, void* stream);
+/* Member i as a batch handle, borrowed from the set (valid until svh_batchset_destroy): svh_batch_read,
+ * svh_batch_plan, svh_batch_fallbacks / _fallback_rows, svh_batch_device_results and a stand-alone
+ * svh_batch_run work on it as on any batch created with SVH_BATCH_NO_TIMING; svh_batch_destroy on it
+ * returns SVH_E_INVALID. */
+int svh_batchset_member(svh_batchset_t s, uint64_t i, svh_batch_t* out);
+int svh_batchset_get_info(svh_batchset_t s, svh_batchset_info* info);
+/* Milliseconds of the last svh_batchset_run: one event pair round the whole run (synchronises). */
+int svh_batchset_elapsed_ms(svh_batchset_t s, float* ms);
+int svh_batchset_destroy(svh_batchset_t s);
 
 /* ---- streaming ingestion (the input side of the path) ------------------ */
 /* .ess: read_emit_seq semantics (data_reader.cpp:93-134).  FASTA: fasta_to_ess.py semantics

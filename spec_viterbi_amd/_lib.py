@@ -69,6 +69,11 @@ class svh_model_info(ctypes.Structure):
     ]
 
 
+class svh_batchset_info(ctypes.Structure):
+    _fields_ = [("members", c_uint64), ("grouped", c_uint64), ("launches", c_uint64), ("grid", c_uint64),
+                ("lds_bytes", c_uint64), ("waves", c_int32)]
+
+
 P_u64 = POINTER(c_uint64)
 P_f32 = POINTER(c_float)
 P_i64 = POINTER(c_int64)
@@ -112,6 +117,13 @@ SIGNATURES = {
     "svh_viterbi_seqs": (c_int, [c_void_p, c_uint32, c_uint64, P_u64, P_u64, P_f32, P_i64, P_i32]),
     "svh_batch_create_u8": (c_int, [c_void_p, c_uint64, P_u64, POINTER(ctypes.c_uint8), c_uint32, POINTER(c_void_p)]),
     "svh_batch_run_time_parallel": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, P_u64]),
+    "svh_batchset_create": (c_int, [POINTER(c_void_p), c_uint64, c_uint64, P_u64, POINTER(ctypes.c_uint8), c_uint32,
+                                    POINTER(c_void_p)]),
+    "svh_batchset_run": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "svh_batchset_member": (c_int, [c_void_p, c_uint64, POINTER(c_void_p)]),
+    "svh_batchset_get_info": (c_int, [c_void_p, POINTER(svh_batchset_info)]),
+    "svh_batchset_elapsed_ms": (c_int, [c_void_p, P_f32]),
+    "svh_batchset_destroy": (c_int, [c_void_p]),
     "svh_reader_open": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
     "svh_reader_next": (c_int, [c_void_p, c_uint64, c_uint64, P_u64, POINTER(P_u64),
                                 POINTER(POINTER(ctypes.c_uint8))]),

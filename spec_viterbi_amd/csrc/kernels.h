@@ -332,6 +332,29 @@ uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths
 bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
+// Model sets (diag.hip diag_set_kernel, runtime.cpp BatchSet): one launch over the workgroups of many
+// (model, batch, scratch) triples.  A table of DiagSetEntry in device memory and a prefix table
+// first[ne + 1] of the entries' first blocks (set_table.h; first[ne] = the grid); a workgroup finds the
+// last entry i with first[i] <= blockIdx.x and runs the plan's body as block blockIdx.x - first[i] of
+// that entry's own launch.  Scores only, models without an X_SF term and with at most 32 symbols, one
+// diagonal per lane, no loader wave; every entry's batch has the same number of sequences (one W per
+// launch).  host[] is the host copy of the table at entries (validated as launch_diag validates its
+// arguments; its largest LDS footprint is the launch's); cus: the device's CUs (even placement, 0: off).
+constexpr uint32_t kDiagSetMaxSym = 32;  // (diag.hip kDMaxSym: the ring's symbol planes)
+struct DiagSetEntry {
+    PipeModel m;
+    FusedBatch b;
+    PipeScratch x;
+};
+struct DiagSetLaunch {
+    uint64_t grid;
+    size_t lds_bytes;  // max over the entries of the plan's own LDS footprint (before even placement)
+    uint32_t waves;
+};
+// what launch_diag_set would launch for this table (hipErrorInvalidValue: an entry it does not take)
+hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out);
+hipError_t launch_diag_set(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, const DiagSetEntry* entries,
+                           const uint32_t* first, uint32_t cus, hipStream_t stream);
 // _spec level 2 on the diagonal plan (diag_l2.hip): every chunk of two observations of every row in
 // one launch -- a lane advances two positions per chunk, so its chain input is again its own score.
 // Row q starts from the first observation's state in b.v_in (row q) and ends in b.scores (row q;

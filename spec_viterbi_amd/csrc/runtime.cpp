@@ -1859,16 +1859,7 @@ Batch::~Batch() {
     if (ev_stop) (void)hipEventDestroy(ev_stop);
 }
 
-void Batch::run(uint32_t level, hipStream_t s) {
-    std::lock_guard<std::mutex> lock(model->mu);
-    DeviceGuard g(model->device);
-    if (!s) s = model->stream;
-    if (paths && level >= 2)
-        throw Error(SVH_E_UNSUPPORTED, "decoded paths are defined for the per-observation recurrence (level <= 1)");
-    if (level >= 2 && model->spec_level != level)
-        throw Error(SVH_E_STATE, "run at _spec level " + std::to_string(level) +
-                                     " needs svh_spec_build(" + std::to_string(level) + ") first");
-    const CsrModel csr = model->csr_view();
+FusedBatch Batch::scores_view() const {
     FusedBatch fb;
     std::memset(&fb, 0, sizeof(fb));
     fb.symbols = p_sym;
@@ -1879,6 +1870,44 @@ void Batch::run(uint32_t level, hipStream_t s) {
     fb.best = p_best;
     fb.fault = p_fault;
     fb.nseq = nseq;
+    return fb;
+}
+
+const DevicePipePlan* Batch::set_plan() const {
+    const DevicePipePlan* dp = paths ? nullptr : model->diag_for(nseq);
+    if (!dp) return nullptr;
+    const PipeModel& v = dp->view;
+    // (the rest: launch_diag's own conditions, which every diagonal table built so far meets)
+    if (v.sx || v.S == 0 || v.S > kDiagSetMaxSym || v.SM != 2 || v.wide || v.nrng == 0 || (size_t)v.nrng * 64 > v.P) return nullptr;
+    return dp;
+}
+
+void Batch::begin_set_run(hipStream_t s, DiagSetEntry* e) {
+    std::lock_guard<std::mutex> lock(model->mu);
+    DeviceGuard g(model->device);
+    const DevicePipePlan* dp = set_plan();
+    if (!dp || !e) throw Error(SVH_E_STATE, "batch set: member is not planned on the diagonal plan");
+    pipe.ensure(nseq, dp->plan.nrng, s);
+    pipe_ran = true;
+    l2_ran = false;
+    last_stream = s;
+    ran = true;
+    e->m = dp->view;
+    e->b = scores_view();  // (FusedBatch::pipe stays null: a host-side field)
+    e->x = pipe.view;
+}
+
+void Batch::run(uint32_t level, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(model->mu);
+    DeviceGuard g(model->device);
+    if (!s) s = own_stream();
+    if (paths && level >= 2)
+        throw Error(SVH_E_UNSUPPORTED, "decoded paths are defined for the per-observation recurrence (level <= 1)");
+    if (level >= 2 && model->spec_level != level)
+        throw Error(SVH_E_STATE, "run at _spec level " + std::to_string(level) +
+                                     " needs svh_spec_build(" + std::to_string(level) + ") first");
+    const CsrModel csr = model->csr_view();
+    FusedBatch fb = scores_view();
     if (paths && chain_paths) {
         fb.cmask = d_cmask.as<uint32_t>();
         fb.cmask_off = p_cmoff;
@@ -2358,7 +2387,7 @@ static bool is_pinned_host(const void* p) {
 
 void Batch::read(hipStream_t s, float* scores, int64_t* best, int32_t* paths_out) {
     DeviceGuard g(model->device);
-    if (!s) s = model->stream;
+    if (!s) s = own_stream();
     if (!ran) throw Error(SVH_E_STATE, "svh_batch_read before svh_batch_run");
     if (paths_out && !paths) throw Error(SVH_E_STATE, "batch was created without SVH_BATCH_PATHS");
     // the fault word, best states and scores (one device arena: one copy) and the paths into
@@ -2459,7 +2488,7 @@ void Model::launch_steps(const FusedBatch& b, bool want_paths, hipStream_t s) co
 
 void Batch::check_fault(hipStream_t s) {
     DeviceGuard g(model->device);
-    if (!s) s = model->stream;
+    if (!s) s = own_stream();
     uint32_t* f = reinterpret_cast<uint32_t*>(h_out.reserve(16));
     hip_check(hipMemcpyAsync(f, p_fault, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "fault D2H");
     hip_check(hipStreamSynchronize(s), "fault D2H");
@@ -2478,7 +2507,7 @@ void Batch::report_fault(uint32_t f, hipStream_t s) {
 
 void Batch::inject_fault(hipStream_t s) {
     DeviceGuard g(model->device);
-    if (!s) s = model->stream;
+    if (!s) s = own_stream();
     if (!ran) throw Error(SVH_E_STATE, "no run recorded");
     hip_check(hipMemsetAsync(p_fault, 0x01, 1, s), "fault inject");  // kFaultPipe
 }

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -13,6 +14,7 @@
 
 #include "error.h"
 #include "kernels.h"
+#include "set_table.h"
 #include "svh.h"
 
 namespace svh {
@@ -331,6 +333,10 @@ struct Batch {
     bool timing = true;
     hipStream_t last_stream = nullptr;
     bool ran = false;
+    // the stream a NULL `stream` argument stands for: the model's, or for a member of a BatchSet the
+    // set's (its first model's), so that a member's read(NULL) waits for the set's run(NULL)
+    hipStream_t set_stream = nullptr;
+    hipStream_t own_stream() const { return set_stream ? set_stream : model->stream; }
 
     // host tables of the last load (copied into h_in)
     Pinned<uint8_t> h_out;  // read(): the result arena and the paths land here in one sync
@@ -368,9 +374,51 @@ struct Batch {
     // diagnostics (svh_batch_debug_fault): mark the last run as if a bounded wait had given up
     void inject_fault(hipStream_t s);
 
+    // BatchSet::run, for a member that runs in the set's launch: what run(level <= 1) does around
+    // launch_steps for a scores batch on the diagonal plan -- the scratch, the flags pipe_fallbacks()
+    // and read() go by -- without the launch; *e = the (model, batch, scratch) triple of that launch
+    void begin_set_run(hipStream_t s, DiagSetEntry* e);
+    // the diagonal plan of this batch's scores pass if a set launch can take it (nullptr: the
+    // member runs on its own): no X_SF term, at most kDiagSetMaxSym symbols
+    const DevicePipePlan* set_plan() const;
+
   private:
     void init(uint32_t flags);
     void report_fault(uint32_t f, hipStream_t s);
+    FusedBatch scores_view() const;  // the inputs and the result arena as the step kernels take them
+};
+
+// Model sets: one batch of sequences scored against many models.  The set owns one Batch per model,
+// each with its own symbols copy, result arena, fault word and scratch, so everything that works on a
+// batch (read, pipe_fallbacks, the plan, the fault report) works on a member unchanged.  run()
+// launches every grouped member -- one whose own scores plan is the diagonal plan, without an X_SF
+// term, of at most kDiagSetMaxSym symbols -- in ONE launch of diag_set_kernel, then every other
+// member's own Batch::run on the same stream.  Levels 0 and 1, scores only.
+struct BatchSet {
+    std::mutex mu;  // run() / info() / elapsed_ms() of one set are serialised
+    std::vector<std::unique_ptr<Batch>> members;
+    std::vector<uint8_t> grouped;  // [members] 1: runs in the set launch
+    int device = 0;
+    uint32_t nseq = 0, cus = 0;
+    bool timing = true;
+    SetTable table;                       // entries = the grouped members, in member order
+    std::vector<DiagSetEntry> h_entries;  // the descriptor table as uploaded
+    DeviceBuffer d_entries, d_first;
+    DiagSetLaunch launch{};
+    uint64_t last_launches = 0;  // of the last run: the set launch and one run per member outside it
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    bool ran = false;
+
+    BatchSet(Model* const* models, uint64_t nmodels, uint64_t nseq, const uint64_t* offsets, const uint8_t* symbols,
+             uint32_t flags);
+    ~BatchSet();
+    void run(uint32_t level, hipStream_t s);
+    svh_batchset_info info();
+    float elapsed_ms();
+
+  private:
+    // every grouped member's begin_set_run; the table is uploaded (on s) when a descriptor changed
+    void refresh(hipStream_t s);
 };
 
 }  // namespace svh

@@ -32,6 +32,12 @@ struct svh_model {
 struct svh_batch {
     std::unique_ptr<svh::Batch> impl;
     svh_model* owner;
+    svh::Batch* view = nullptr;  // a set's member (svh_batchset_member): borrowed, impl is empty
+    svh::Batch* get() const { return view ? view : impl.get(); }
+};
+struct svh_batchset {
+    std::unique_ptr<svh::BatchSet> impl;
+    std::vector<std::unique_ptr<svh_batch>> views;  // the members' borrowed handles
 };
 struct svh_reader {
     std::unique_ptr<svh::SeqReader> impl;
@@ -230,7 +236,7 @@ int svh_batch_create_u8(svh_model_t m, uint64_t nseq, const uint64_t* offsets, c
 int svh_batch_run(svh_batch_t b, uint32_t level, void* stream) {
     return guarded([&] {
         require(b != nullptr, "null batch");
-        b->impl->run(level, static_cast<hipStream_t>(stream));
+        b->get()->run(level, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -238,7 +244,7 @@ int svh_batch_run_time_parallel(svh_batch_t b, uint32_t seg_len, uint32_t probe_
                                 void* stream, uint64_t* fallbacks) {
     return guarded([&] {
         require(b != nullptr, "null batch");
-        b->impl->run_time_parallel(seg_len, probe_len, rel_tol, static_cast<hipStream_t>(stream), fallbacks);
+        b->get()->run_time_parallel(seg_len, probe_len, rel_tol, static_cast<hipStream_t>(stream), fallbacks);
     });
 }
 
@@ -260,43 +266,43 @@ int svh_batch_read(svh_batch_t b, void* stream, float* scores, int64_t* best_sta
                    int32_t* paths) {
     return guarded([&] {
         require(b != nullptr, "null batch");
-        b->impl->read(static_cast<hipStream_t>(stream), scores, best_state, paths);
+        b->get()->read(static_cast<hipStream_t>(stream), scores, best_state, paths);
     });
 }
 
 int svh_batch_device_results(svh_batch_t b, float** scores, int64_t** best_state) {
     return guarded([&] {
         require(b != nullptr, "null batch");
-        if (scores) *scores = b->impl->p_scores;
-        if (best_state) *best_state = b->impl->p_best;
+        if (scores) *scores = b->get()->p_scores;
+        if (best_state) *best_state = b->get()->p_best;
     });
 }
 
 int svh_batch_elapsed_ms(svh_batch_t b, float* ms) {
     return guarded([&] {
         require(b && ms, "null argument");
-        *ms = b->impl->elapsed_ms();
+        *ms = b->get()->elapsed_ms();
     });
 }
 
 int svh_batch_step_floor_ms(svh_batch_t b, void* stream, uint32_t reps, float* ms) {
     return guarded([&] {
         require(b && ms && reps > 0, "null argument or reps == 0");
-        *ms = b->impl->step_floor_ms(static_cast<hipStream_t>(stream), reps);
+        *ms = b->get()->step_floor_ms(static_cast<hipStream_t>(stream), reps);
     });
 }
 
 int svh_batch_fallback_rows(svh_batch_t b, uint32_t* flags) {
     return guarded([&] {
         require(b && flags, "null argument");
-        (void)b->impl->pipe_fallbacks(flags);
+        (void)b->get()->pipe_fallbacks(flags);
     });
 }
 
 int svh_batch_fallbacks(svh_batch_t b, uint64_t* rows) {
     return guarded([&] {
         require(b && rows, "null argument");
-        *rows = b->impl->pipe_fallbacks();
+        *rows = b->get()->pipe_fallbacks();
     });
 }
 
@@ -313,19 +319,79 @@ int svh_pipe_variant_built(int32_t slots, int32_t waves, int32_t table_mode, int
 int svh_batch_debug_fault(svh_batch_t b, void* stream) {
     return guarded([&] {
         require(b != nullptr, "null batch");
-        b->impl->inject_fault(static_cast<hipStream_t>(stream));
+        b->get()->inject_fault(static_cast<hipStream_t>(stream));
     });
 }
 
 int svh_batch_plan(svh_batch_t b, uint32_t level, svh_model_info* info) {
     return guarded([&] {
         require(b && info, "null argument");
-        *info = b->impl->model->info(b->impl->nseq, b->impl->paths, level);
+        *info = b->get()->model->info(b->get()->nseq, b->get()->paths, level);
     });
 }
 
 int svh_batch_destroy(svh_batch_t b) {
-    return guarded([&] { delete b; });
+    return guarded([&] {
+        if (b && b->view) throw svh::Error(SVH_E_INVALID, "a set's member is destroyed with its set (svh_batchset_destroy)");
+        delete b;
+    });
+}
+
+// ---- model sets ----------------------------------------------------------------------------
+int svh_batchset_create(const svh_model_t* models, uint64_t nmodels, uint64_t nseq, const uint64_t* offsets,
+                        const uint8_t* symbols, uint32_t flags, svh_batchset_t* out) {
+    return guarded([&] {
+        require(models && out, "null argument");
+        *out = nullptr;
+        std::vector<svh::Model*> ms(nmodels);
+        for (uint64_t i = 0; i < nmodels; ++i) {
+            require(models[i] != nullptr, "null model");
+            ms[i] = models[i]->impl.get();
+        }
+        auto s = std::make_unique<svh_batchset>();
+        s->impl = std::make_unique<svh::BatchSet>(ms.data(), nmodels, nseq, offsets, symbols, flags);
+        for (uint64_t i = 0; i < nmodels; ++i) {
+            auto v = std::make_unique<svh_batch>();
+            v->owner = models[i];
+            v->view = s->impl->members[i].get();
+            s->views.push_back(std::move(v));
+        }
+        *out = s.release();
+    });
+}
+
+int svh_batchset_run(svh_batchset_t s, uint32_t level, void* stream) {
+    return guarded([&] {
+        require(s != nullptr, "null batch set");
+        s->impl->run(level, static_cast<hipStream_t>(stream));
+    });
+}
+
+int svh_batchset_member(svh_batchset_t s, uint64_t i, svh_batch_t* out) {
+    return guarded([&] {
+        require(s && out, "null argument");
+        *out = nullptr;
+        if (i >= s->views.size()) throw svh::Error(SVH_E_RANGE, "batch set: member index out of range");
+        *out = s->views[i].get();
+    });
+}
+
+int svh_batchset_get_info(svh_batchset_t s, svh_batchset_info* info) {
+    return guarded([&] {
+        require(s && info, "null argument");
+        *info = s->impl->info();
+    });
+}
+
+int svh_batchset_elapsed_ms(svh_batchset_t s, float* ms) {
+    return guarded([&] {
+        require(s && ms, "null argument");
+        *ms = s->impl->elapsed_ms();
+    });
+}
+
+int svh_batchset_destroy(svh_batchset_t s) {
+    return guarded([&] { delete s; });
 }
 
 namespace {

@@ -250,7 +250,83 @@ class DeviceBatch:
 
     def close(self):
         if getattr(self, "_h", None):
-            _lib.lib.svh_batch_destroy(self._h)
+            if not getattr(self, "_borrowed", False):  # (a set's member is destroyed with its set)
+                _lib.lib.svh_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceModelSet:
+    """Models on one device that batches of sequences are scored against together (svh_batchset_*).
+    The models stay the caller's: the set keeps references, closes none."""
+
+    def __init__(self, models):
+        self.models = list(models)
+        if not self.models:
+            raise ValueError("DeviceModelSet: no models")
+
+    def batch(self, seqs, timing: bool = True) -> "DeviceBatchSet":
+        return DeviceBatchSet(self, seqs, timing)
+
+
+class DeviceBatchSet:
+    """One batch of sequences resident in HBM once per model of a DeviceModelSet; run() scores every
+    member: those whose own plan is the diagonal plan (no term from the feeder to the sink row, at
+    most 32 symbols) in ONE launch, the others with their own run on the same stream.  Scores only,
+    levels 0 and 1; results are bit for bit those of the members' stand-alone runs."""
+
+    def __init__(self, mset: DeviceModelSet, seqs, timing: bool = True, paths: bool = False):
+        self.mset = mset
+        self.offsets, sym64 = pack_sequences(seqs)
+        self.nseq = self.offsets.size - 1
+        if sym64.size and int(sym64.max()) > 255:
+            raise _lib.SvhError(_lib.SVH_E_RANGE, f"symbol {int(sym64.max())} out of range (a set takes 8-bit symbols)")
+        symbols = np.ascontiguousarray(sym64, np.uint8)
+        handles = (ctypes.c_void_p * len(mset.models))(*[m.handle for m in mset.models])
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib.svh_batchset_create(handles, len(mset.models), self.nseq, _p(self.offsets, _u64),
+                                                _p(symbols, ctypes.POINTER(ctypes.c_uint8)),
+                                                (0 if timing else _lib.SVH_BATCH_NO_TIMING) |
+                                                (_lib.SVH_BATCH_PATHS if paths else 0), ctypes.byref(h)))
+        self._h = h
+        self.members = []
+        for i, model in enumerate(mset.models):
+            bh = ctypes.c_void_p()
+            _lib.check(_lib.lib.svh_batchset_member(self._h, i, ctypes.byref(bh)))
+            b = DeviceBatch.__new__(DeviceBatch)  # a view: the handle is the set's
+            b.model, b.offsets, b.nseq, b.paths, b.total = model, self.offsets, self.nseq, False, int(self.offsets[-1])
+            b._h, b._borrowed = bh, True
+            self.members.append(b)
+
+    def run(self, level: int = 0, stream: int | None = None) -> None:
+        _lib.check(_lib.lib.svh_batchset_run(self._h, int(level), ctypes.c_void_p(stream or 0)))
+
+    def read(self, stream: int | None = None) -> list:
+        """[(scores [nseq, n_i], best [nseq])] per member, in model order."""
+        return [b.read(stream) for b in self.members]
+
+    def info(self) -> dict:
+        """members, grouped (members in the set's one launch), launches (of the last run: that launch
+        plus one run per member outside it), grid, lds_bytes and waves of the set launch."""
+        i = _lib.svh_batchset_info()
+        _lib.check(_lib.lib.svh_batchset_get_info(self._h, ctypes.byref(i)))
+        return {name: getattr(i, name) for name, _ in i._fields_}
+
+    def elapsed_ms(self) -> float:
+        ms = ctypes.c_float()
+        _lib.check(_lib.lib.svh_batchset_elapsed_ms(self._h, ctypes.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for b in self.members:
+                b._h = None
+            _lib.lib.svh_batchset_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -71,12 +71,60 @@ def timed(fn, runs=RUNS):
     return statistics.median(out)
 
 
+def sweep_set(models, data, sink):
+    """--set: the level-0 cells of one dataset in one model-set run (svh_batchset_run: the models on
+    the diagonal plan in one launch, the others after it); `ms_set` is the median wall time of that
+    run with every member's scores back on the host, shared by the dataset's cells; each cell is
+    checked as the per-cell sweep checks it."""
+    hmms = [svh.read_HMM(os.path.join(ROOT, "data", "chmm_files", name)) for name in models]
+    dev = [svh.DeviceModel(h) for h in hmms]
+    mset = svh.DeviceModelSet(dev)
+    for dname, seqs in data.items():
+        bs = mset.batch(seqs)
+
+        def once():
+            bs.run()
+            return bs.read()
+
+        once()  # warm-up
+        ms = timed(once)
+        res = once()
+        info = bs.info()
+        obs = sum(int(s.size) for s in seqs)
+        for i, name in enumerate(models):
+            scores = res[i][0]
+            ref = digest_rows(name, dname, 0)
+            if ref is not None:
+                ok = len(ref) == len(seqs) and all(
+                    hashlib.sha256(np.ascontiguousarray(scores[q], np.float32).tobytes()).hexdigest() == ref[q]
+                    for q in range(len(seqs)))
+                check = "digests" if ok else "MISMATCH"
+            else:
+                ok = bit_equal(scores[0], oracle.viterbi(hmms[i], seqs[0]))
+                check = "bit-exact" if ok else "MISMATCH"
+            rec = {"model": name, "states": int(hmms[i].states_num), "dataset": dname, "sequences": len(seqs),
+                   "observations": obs, "level": 0, "set": True, "ms_set": round(ms, 3), "set_members": info["members"],
+                   "set_grouped": info["grouped"], "set_launches": info["launches"], "set_grid": info["grid"],
+                   "kernel": bs.members[i].plan()["kernel"], "fallback_rows": bs.members[i].fallbacks(), "check": check}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if sink:
+                sink.write(line + "\n")
+                sink.flush()
+            if not ok:
+                raise SystemExit(f"bench_sweep: {name} x {dname} (set): output check failed")
+        bs.close()
+    for m in dev:
+        m.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--models", default="")
     p.add_argument("--datasets", default=",".join(DATASETS))
     p.add_argument("--levels", default="0,1,2")
     p.add_argument("--out", default="")
+    p.add_argument("--set", action="store_true", help="level 0 only: each dataset's cells in one model-set run")
     a = p.parse_args()
     models = a.models.split(",") if a.models else sorted(
         (os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "data", "chmm_files", "*.chmm"))),
@@ -84,6 +132,9 @@ def main():
     levels = [int(x) for x in a.levels.split(",")]
     sink = open(a.out, "w") if a.out else None
     data = {d: svh.read_emit_seq(os.path.join(ROOT, "data", "ess_files", d)) for d in a.datasets.split(",")}
+    if a.set:
+        sweep_set(models, data, sink)
+        return
     for name in models:
         hmm = svh.read_HMM(os.path.join(ROOT, "data", "chmm_files", name))
         n = int(hmm.states_num)
