@@ -1052,7 +1052,7 @@ Model::Model(const HostModel& h, const svh_model_opts* opts) : host(h) {
     int dev = opts ? opts->device : -1;
     if (dev < 0) hip_check(hipGetDevice(&dev), "hipGetDevice");
     device = dev;
-    kernel_pref = opts ? opts->kernel : SVH_KERNEL_AUTO;
+    const int kernel_pref = opts ? opts->kernel : SVH_KERNEL_AUTO;
     if (kernel_pref < SVH_KERNEL_AUTO || (kernel_pref > SVH_KERNEL_PIPE_WIDE && kernel_pref != SVH_KERNEL_DIAG))
         throw Error(SVH_E_INVALID, "kernel must be one of SVH_KERNEL_AUTO .. SVH_KERNEL_PIPE_WIDE or SVH_KERNEL_DIAG");
     if (opts && (opts->flags & ~SVH_MODEL_SPEC_DENSE))
@@ -1112,9 +1112,9 @@ Model::Model(const HostModel& h, const svh_model_opts* opts) : host(h) {
             // one (the path kernel's 290 registers fit once); wider batches run the wide pipelined plan
             // (DESIGN.md 5c), or the chain kernel where the model has none; SVH_PIPE_MAX_NSEQ
             // overrides the scores-only bound
-            pipe_max_nseq = std::max<uint32_t>(1, 2 * cu_count / pipe.plan.G);
-            pipe_max_nseq_paths = std::max<uint32_t>(1, cu_count / pipe.plan.G);
-            if (const char* e = std::getenv("SVH_PIPE_MAX_NSEQ")) pipe_max_nseq = (uint32_t)std::atoi(e);
+            caps.pipe_max_nseq = std::max<uint32_t>(1, 2 * cu_count / pipe.plan.G);
+            caps.pipe_max_nseq_paths = std::max<uint32_t>(1, cu_count / pipe.plan.G);
+            if (const char* e = std::getenv("SVH_PIPE_MAX_NSEQ")) caps.pipe_max_nseq = (uint32_t)std::atoi(e);
             // diagonal plan (diag.hip): the scores-only batches the latency plan would take (DESIGN.md
             // 5l); SVH_DIAG=0 disables it, SVH_DIAG_MAX_NSEQ overrides the bound
             if (pipe.view.dtab && !(std::getenv("SVH_DIAG") && std::atoi(std::getenv("SVH_DIAG")) == 0)) {
@@ -1123,14 +1123,14 @@ Model::Model(const HostModel& h, const svh_model_opts* opts) : host(h) {
                 // at 64 the diagonal plan takes 0.296 ms against 0.303, at 90 0.363 against 0.313,
                 // profiles/r06_diag/widths.log)
                 const uint32_t w = diag_waves_for(4);
-                diag_max_nseq = std::min<uint32_t>(pipe_max_nseq, w * (2 * cu_count / pipe.plan.nrng));
-                if (const char* e = std::getenv("SVH_DIAG_MAX_NSEQ")) diag_max_nseq = (uint32_t)std::atoi(e);
+                caps.diag_max_nseq = std::min<uint32_t>(caps.pipe_max_nseq, w * (2 * cu_count / pipe.plan.nrng));
+                if (const char* e = std::getenv("SVH_DIAG_MAX_NSEQ")) caps.diag_max_nseq = (uint32_t)std::atoi(e);
             }
         }
         if (pipe_wide.plan.ok) {
             // AUTO: the wide pipelined plan for batches beyond the latency plan's range
-            pipew_min_nseq = pipe_max_nseq + 1;
-            if (const char* e = std::getenv("SVH_PIPEW_MIN_NSEQ")) pipew_min_nseq = (uint32_t)std::atoi(e);
+            caps.pipew_min_nseq = caps.pipe_max_nseq + 1;
+            if (const char* e = std::getenv("SVH_PIPEW_MIN_NSEQ")) caps.pipew_min_nseq = (uint32_t)std::atoi(e);
         }
     }
     Plan fast = make_plan(host, max_threads, true);
@@ -1149,6 +1149,33 @@ Model::Model(const HostModel& h, const svh_model_opts* opts) : host(h) {
         paths_plan = &paths_plan_storage;
     } else {
         paths_plan = &fast_plan;
+    }
+    // what the dispatch goes by (dispatch.h): every answer taken here, once
+    caps.kernel_pref = kernel_pref;
+    caps.band_ok = band.plan.ok;
+    caps.band_chain = band.plan.chain;
+    caps.band_paths_ok = band.plan.paths_ok();
+    caps.band_wide_ok = band_wide.plan.ok;
+    caps.fused_scores = fast_plan.plan.fused;
+    caps.fused_paths = paths_plan->plan.fused;
+    caps.pipe_ok = pipe.plan.ok;
+    caps.pipew_ok = pipe_wide.plan.ok;
+    caps.dtab = pipe.view.dtab != nullptr;
+    caps.pipe_G = pipe.plan.G;
+    caps.pipew_G = pipe_wide.plan.G;
+    caps.diag_nrng = pipe.plan.nrng;
+    caps.pipe_rerun = pipe.view.rerun != 0;
+    caps.cu_count = cu_count;
+    {
+        const PipePlan &p = pipe.plan, &w = pipe_wide.plan;
+        // SVH_PIPEW_PATHS=0 sends wide path batches to the chain kernel (A/B; process-wide, read once)
+        static const bool wide_env = !(std::getenv("SVH_PIPEW_PATHS") && std::atoi(std::getenv("SVH_PIPEW_PATHS")) == 0);
+        caps.pipe_paths_ok = p.ok && pipe_paths_supported((int)p.SM, (int)p.W) && p.P <= kPipeTbMaxP;
+        caps.pipew_paths_ok = wide_env && w.ok && w.P <= kPipeTbMaxP && pipew_paths_supported((int)w.SM, host.S, w.sx);
+        caps.diag_paths_ok = p.ok && p.ties_heavy && !p.wide && p.P <= kPipeTbMaxP && host.n <= kPipeTbMaxP + 2 &&
+                             host.S <= 32 && (uint64_t)p.nrng * 64 <= p.P && diag_paths_fit(host.S, p.sx);
+        caps.pipe_l2_ok = p.ok && pipe_l2_supported(pipe.view);
+        caps.diag_l2_ok = p.ok && diag_l2_supported(pipe.view);
     }
 
     std::vector<uint32_t> row_of(host.nnz());
@@ -1188,74 +1215,16 @@ CsrModel Model::csr_view() const {
     return c;
 }
 
-const DeviceBandPlan* Model::band_for(bool paths, uint32_t nseq) const {
-    if (!band.plan.ok) return nullptr;
-    if (kernel_pref != SVH_KERNEL_AUTO && kernel_pref != SVH_KERNEL_BAND && kernel_pref != SVH_KERNEL_CHAIN &&
-        kernel_pref != SVH_KERNEL_PIPE && kernel_pref != SVH_KERNEL_PIPE_WIDE && kernel_pref != SVH_KERNEL_DIAG)
-        // PIPE*, DIAG: the chain plan is their fallback (paths, the _spec tail)
-        return nullptr;
-    if (paths) return band.plan.paths_ok() ? &band : nullptr;  // decoded-path chain variant
-    if (band_wide.plan.ok && nseq > cu_count) return &band_wide;
-    return &band;
+PassPlan Model::resolve(uint32_t rows, bool paths, uint32_t level, bool scratch) const {
+    return resolve_pass(caps, PassQuery{rows, paths, level, spec_level, spec2_on, scratch});
 }
 
-const DevicePipePlan* Model::pipe_for(uint32_t nseq) const {
-    if (kernel_pref == SVH_KERNEL_PIPE) return pipe.plan.ok ? &pipe : nullptr;
-    if (kernel_pref == SVH_KERNEL_PIPE_WIDE) return pipe_wide.plan.ok ? &pipe_wide : nullptr;
-    if (kernel_pref != SVH_KERNEL_AUTO) return nullptr;
-    if (pipe.plan.ok && nseq <= pipe_max_nseq) return &pipe;
-    if (pipe_wide.plan.ok && nseq >= pipew_min_nseq) return &pipe_wide;
-    return nullptr;
+const DeviceBandPlan* Model::band_plan(const PassPlan& p) const {
+    return !on_band(p.step) ? nullptr : p.band_wide ? &band_wide : &band;
 }
 
-const DevicePipePlan* Model::diag_for(uint32_t nseq) const {
-    if (!pipe.plan.ok || !pipe.view.dtab) return nullptr;
-    if (kernel_pref == SVH_KERNEL_DIAG) return &pipe;
-    if (kernel_pref != SVH_KERNEL_AUTO) return nullptr;
-    return nseq <= diag_max_nseq ? &pipe : nullptr;
-}
-
-// Decoded paths: the latency plan's path variant for the batches its scores pass takes, the wide
-// plan's beyond that (the chain kernel's path variant is the exact fallback of both, so the model
-// needs its plan too); SVH_PIPEW_PATHS=0 sends wide path batches to the chain kernel (A/B).
-const DevicePipePlan* Model::pipe_paths_for(uint32_t nseq) const {
-    if (!band.plan.paths_ok()) return nullptr;
-    const bool lat = pipe.plan.ok && pipe_paths_supported((int)pipe.plan.SM, (int)pipe.plan.W) &&
-                     pipe.plan.P <= kPipeTbMaxP;
-    static const bool wide_env = !(std::getenv("SVH_PIPEW_PATHS") && std::atoi(std::getenv("SVH_PIPEW_PATHS")) == 0);
-    const bool wid = wide_env && pipe_wide.plan.ok && pipe_wide.plan.P <= kPipeTbMaxP &&
-                     pipew_paths_supported((int)pipe_wide.plan.SM, host.S, pipe_wide.plan.sx);
-    if (kernel_pref == SVH_KERNEL_PIPE) return lat ? &pipe : nullptr;
-    if (kernel_pref == SVH_KERNEL_PIPE_WIDE) return wid ? &pipe_wide : nullptr;
-    if (kernel_pref != SVH_KERNEL_AUTO) return nullptr;
-    if (lat && nseq <= pipe_max_nseq_paths) return &pipe;
-    if (wid && nseq > pipe_max_nseq_paths) return &pipe_wide;
-    return nullptr;
-}
-
-const DevicePipePlan* Model::diag_paths_for(uint32_t nseq) const {
-    (void)nseq;
-    if (kernel_pref != SVH_KERNEL_DIAG || !pipe.plan.ok || !pipe.view.dtab || !band.plan.paths_ok()) return nullptr;
-    const PipePlan& p = pipe.plan;
-    if (!p.ties_heavy || p.wide || p.P > kPipeTbMaxP || host.n > kPipeTbMaxP + 2 || host.S > 32 ||
-        (uint64_t)p.nrng * 64 > p.P || !diag_paths_fit(host.S, p.sx))
-        return nullptr;
-    return &pipe;
-}
-
-bool Model::pipe_l2_on() const {
-    return spec2_on && pipe.plan.ok && pipe_l2_supported(pipe.view) &&
-           (kernel_pref == SVH_KERNEL_AUTO || kernel_pref == SVH_KERNEL_PIPE);
-}
-
-bool Model::diag_l2_on() const {
-    return kernel_pref == SVH_KERNEL_DIAG && spec2_on && pipe.plan.ok && diag_l2_supported(pipe.view);
-}
-
-const DevicePlan* Model::plan_for(bool paths) const {
-    if (kernel_pref == SVH_KERNEL_GENERIC) return nullptr;
-    const DevicePlan* p = paths ? paths_plan : &fast_plan;
-    return (p && p->plan.fused) ? p : nullptr;
+const DevicePlan* Model::fused_plan(bool paths) const {
+    return !fused_usable(caps, paths) ? nullptr : paths ? paths_plan : &fast_plan;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1494,16 +1463,22 @@ void Model::spec_build(uint32_t level, hipStream_t s) {
     spec_level = level;
 }
 
+// What the pass over nseq rows at `level` would run (nseq 0: the model alone), as layers: the fused
+// plan's fields, under the chain plan's, under the pipelined or diagonal plan's, under the chunk
+// route's -- each layer only where the resolved plan has it.
 svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
     svh_model_info i;
     std::memset(&i, 0, sizeof(i));
-    const bool steps = level <= 1 || spec_level < 2;  // level >= 2 runs only the tail on step kernels
-    const DevicePlan* p = plan_for(paths && steps);
-    const DeviceBandPlan* bpl = band_for(paths && steps, nseq);
-    i.kernel = bpl ? (bpl->plan.chain ? SVH_KERNEL_CHAIN : SVH_KERNEL_BAND) : p ? SVH_KERNEL_FUSED : SVH_KERNEL_GENERIC;
-    // the pipelined plan runs scores-only passes, the step-kernel tail of _spec level >= 2 and
-    // (latency plan) decoded-path passes of small batches
-    const DevicePipePlan* ppl = !nseq ? nullptr : !paths ? pipe_for(nseq) : steps ? pipe_paths_for(nseq) : nullptr;
+    // level >= 2 runs only the tail on step kernels, and no decoded paths: a path batch then reports
+    // the scores plan of a view without scratch
+    const bool steps = level <= 1 || spec_level < 2;
+    const bool pq = paths && steps;
+    const PassPlan pl = resolve(nseq, pq, level, nseq != 0 && pq == paths);
+    // (the tail's launch is the diagonal kernel where pl.step says so; the name reported at level >= 2
+    // leaves the diagonal plan out and only diag_sm tells of it: dispatch.cpp)
+    const StepKernel named = level >= 2 ? pl.no_diag : pl.step;
+    const DevicePlan* p = fused_plan(pq);
+    i.kernel = kernel_id(named);
     i.family = p ? p->plan.family : -1;
     i.threads = p ? (int32_t)p->plan.B : (int32_t)std::min<uint32_t>(1024, round_up(host.n, 64));
     i.slots = p ? (int32_t)p->plan.SM : 0;
@@ -1515,7 +1490,7 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
     i.S = host.S;
     i.nnz = host.nnz();
     i.lds_bytes = p ? p->plan.lds_bytes : generic_lds_bytes(host.n);
-    if (bpl) {
+    if (const DeviceBandPlan* bpl = band_plan(pl)) {
         i.threads = (int32_t)bpl->plan.B;
         i.slots = (int32_t)bpl->plan.SM;
         i.light_terms = (int32_t)bpl->plan.HA + 1;
@@ -1525,73 +1500,64 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
     }
     i.spec_level = spec_level;
     i.spec_bytes = d_products.bytes;
-    const DevicePipePlan* pp1 = pipe_paths_for(1);
-    i.paths_kernel = diag_paths_for(1) ? SVH_KERNEL_DIAG
-                     : pp1 ? (pp1->plan.wide ? SVH_KERNEL_PIPE_WIDE : SVH_KERNEL_PIPE)
-                     : band_for(true) ? SVH_KERNEL_CHAIN : plan_for(true) ? SVH_KERNEL_FUSED : SVH_KERNEL_GENERIC;
-    i.wide_threads = band_wide.plan.ok && band_for(false) ? (int32_t)band_wide.plan.B : 0;
-    i.wide_slots = band_wide.plan.ok && band_for(false) ? (int32_t)band_wide.plan.SM : 0;
+    i.paths_kernel = kernel_id(resolve(1, true, 0, true).step);
+    const bool wide_chain = band_wide.plan.ok && on_band(resolve(0, false, 0, false).step);
+    i.wide_threads = wide_chain ? (int32_t)band_wide.plan.B : 0;
+    i.wide_slots = wide_chain ? (int32_t)band_wide.plan.SM : 0;
     i.cu_count = cu_count;
-    if (ppl) {
-        uint32_t w = ppl->plan.wide ? pipew_waves_for(ppl->view, nseq) : ppl->plan.W;
-        if (ppl->plan.wide && paths) w = std::min(w, pipew_paths_waves_max(ppl->plan.SM, host.S, ppl->plan.sx));
-        i.kernel = ppl->plan.wide ? SVH_KERNEL_PIPE_WIDE : SVH_KERNEL_PIPE;
+    if (pipelined(named)) {
+        const DevicePipePlan& ppl = named == StepKernel::PipeWide ? pipe_wide : pipe;
+        uint32_t w = ppl.plan.wide ? pipew_waves_for(ppl.view, nseq) : ppl.plan.W;
+        if (ppl.plan.wide && paths) w = std::min(w, pipew_paths_waves_max(ppl.plan.SM, host.S, ppl.plan.sx));
         i.threads = (int32_t)(64 * w);
-        i.slots = (int32_t)ppl->plan.SM;
-        i.lds_bytes = ppl->plan.wide ? pipew_lds_bytes(ppl->plan.SM, w, host.S, ppl->plan.sx, paths)
-                                     : pipe_lds_bytes(ppl->plan.W, host.S);
+        i.slots = (int32_t)ppl.plan.SM;
+        i.lds_bytes = ppl.plan.wide ? pipew_lds_bytes(ppl.plan.SM, w, host.S, ppl.plan.sx, paths)
+                                    : pipe_lds_bytes(ppl.plan.W, host.S);
     }
+    const ReportedThresholds t = reported_thresholds(caps);
     if (pipe_wide.plan.ok) {
         i.pipew_slots = (int32_t)pipe_wide.plan.SM;
         i.pipew_waves = (int32_t)pipe_wide.plan.W;
         i.pipew_blocks = (int32_t)pipe_wide.plan.G;
-        i.pipew_min_nseq = kernel_pref == SVH_KERNEL_PIPE_WIDE ? 0u
-                           : kernel_pref == SVH_KERNEL_AUTO    ? pipew_min_nseq
-                                                               : 0xFFFFFFFFu;
     }
     if (pipe.plan.ok) {
         i.pipe_slots = (int32_t)pipe.plan.SM;
         i.pipe_waves = (int32_t)pipe.plan.W;
         i.pipe_groups = (int32_t)pipe.plan.G;
-        i.pipe_max_nseq = kernel_pref == SVH_KERNEL_PIPE ? 0xFFFFFFFFu : pipe_max_nseq;
-        i.pipe_max_nseq_paths = kernel_pref == SVH_KERNEL_PIPE ? 0xFFFFFFFFu : pipe_max_nseq_paths;
     }
-    if (!paths && steps && level <= 1 && nseq && diag_for(nseq)) {  // scores on the diagonal plan
+    if (pipe.view.dtab) i.diag_ranges = (int32_t)pipe.plan.nrng;
+    i.pipe_max_nseq = t.pipe_max_nseq;
+    i.pipe_max_nseq_paths = t.pipe_max_nseq_paths;
+    i.pipew_min_nseq = t.pipew_min_nseq;
+    i.diag_max_nseq = t.diag_max_nseq;
+    if (pl.step == StepKernel::Diag && level <= 1) {
         const uint32_t w = diag_waves_for(nseq);
-        i.kernel = SVH_KERNEL_DIAG;
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
-        i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
-        i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm, diag_loader_for(pipe.view, nseq, false, false));
-    } else if (!paths && level >= 2 && nseq && diag_for(nseq)) {  // the _spec tail's launch
+        if (!pq) {  // scores on the diagonal plan
+            i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
+            i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm, diag_loader_for(pipe.view, nseq, false, false));
+        } else {  // decoded paths on the diagonal plan
+            i.diag_sm = 1;
+            i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);
+        }
+    } else if (pl.step == StepKernel::Diag && !pq) {  // the _spec tail's launch
         i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, true, false);
     }
-    if (paths && steps && level <= 1 && nseq && diag_paths_for(nseq)) {  // decoded paths on the diagonal plan
-        const uint32_t w = diag_waves_for(nseq);
-        i.kernel = SVH_KERNEL_DIAG;
-        i.threads = (int32_t)(64 * w);
-        i.slots = 1;
-        i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);
-        i.diag_sm = 1;
-    }
-    if (pipe.view.dtab) {
-        i.diag_ranges = (int32_t)pipe.plan.nrng;
-        i.diag_max_nseq = kernel_pref == SVH_KERNEL_DIAG ? 0xFFFFFFFFu : kernel_pref == SVH_KERNEL_AUTO ? diag_max_nseq : 0u;
-    }
-    if (level == 2 && spec_level == 2 && nseq && pipe_l2_on()) {  // the chunks on the pipelined plan
+    if (nseq && pl.chunks == ChunkRoute::Spec2Pipe) {  // the chunks on the pipelined plan
         i.kernel = SVH_KERNEL_SPEC2_PIPE;
         i.threads = (int32_t)(64 * pipe.plan.W);
         i.slots = (int32_t)pipe.plan.SM;
         i.lds_bytes = pipe_lds_bytes(pipe.plan.W, host.S);
         i.spec_bytes = 0;
-    } else if (level == 2 && spec_level == 2 && nseq && diag_l2_on()) {  // the chunks on the diagonal plan
+    } else if (nseq && pl.chunks == ChunkRoute::Spec2Diag) {  // the chunks on the diagonal plan
         const uint32_t w = diag_waves_for(nseq);
         i.kernel = SVH_KERNEL_SPEC2_DIAG;
         i.threads = (int32_t)(64 * w);
         i.slots = 1;
         i.lds_bytes = diag_l2_lds_bytes(w, host.S);
         i.spec_bytes = 0;
-    } else if (level == 2 && spec_level == 2 && spec2_on && nseq) {  // the chunks run on chip (spec2.hip)
+    } else if (nseq && pl.chunks == ChunkRoute::Spec2) {  // the chunks run on chip (spec2.hip)
         const Spec2Plan& sp = spec2.plan;
         i.kernel = SVH_KERNEL_SPEC2;
         i.threads = (int32_t)kSpec2Threads;
@@ -1624,8 +1590,8 @@ Batch::Batch(Model* m, uint64_t nseq_, const uint64_t* offs, const uint8_t* symb
 
 void Batch::init(uint32_t flags) {
     paths = (flags & SVH_BATCH_PATHS) != 0;
-    chain_paths = paths && model->band_for(true) != nullptr;
-    if (paths && !chain_paths && model->host.n >= kNoPred)
+    // (backpointers or the chain kernel's records is fixed per model: load() finds the same at every width)
+    if (paths && model->resolve(1, true, 0, true).records == PathRecords::Backpointers && model->host.n >= kNoPred)
         throw Error(SVH_E_UNSUPPORTED, "paths need states_num < 65535 for models the chain kernel does not cover");
     timing = (flags & SVH_BATCH_NO_TIMING) == 0;
     DeviceGuard g(model->device);
@@ -1646,12 +1612,15 @@ void Batch::load(uint64_t nseq_, const uint64_t* offs, const uint64_t* sym64, co
     if (seqp)
         for (uint64_t q = 0; q < nseq_; ++q)
             if (!seqp[q] && offs[q + 1] > offs[q]) throw Error(SVH_E_INVALID, "null sequence pointer");
-    const DeviceBandPlan* cpl = chain_paths ? model->band_for(true) : nullptr;
     nseq = (uint32_t)nseq_;
-    const DevicePipePlan* ppl = chain_paths ? model->pipe_paths_for(nseq) : nullptr;
-    pipe_paths = ppl != nullptr;
-    const DevicePipePlan* dpl = chain_paths && !ppl ? model->diag_paths_for(nseq) : nullptr;
-    diag_paths = dpl != nullptr;
+    // the level <= 1 pass of these sequences: run() goes by it, the record buffers are sized from it
+    plan = model->resolve(nseq, paths, 0, true);
+    chain_paths = paths && plan.records != PathRecords::Backpointers;
+    pipe_paths = plan.records == PathRecords::Pipe;
+    diag_paths = plan.records == PathRecords::Diag;
+    const DeviceBandPlan* cpl = chain_paths ? model->band_plan(plan) : nullptr;
+    const DevicePipePlan* ppl = pipe_paths ? &model->pipe_plan(plan) : nullptr;
+    const DevicePipePlan* dpl = diag_paths ? &model->pipe_plan(plan) : nullptr;
     const bool recs = pipe_paths || diag_paths;  // the four record buffers of either plan
     offsets.assign(offs, offs + nseq + 1);
     lens.resize(nseq);
@@ -1874,8 +1843,8 @@ FusedBatch Batch::scores_view() const {
 }
 
 const DevicePipePlan* Batch::set_plan() const {
-    const DevicePipePlan* dp = paths ? nullptr : model->diag_for(nseq);
-    if (!dp) return nullptr;
+    if (paths || plan.step != StepKernel::Diag) return nullptr;
+    const DevicePipePlan* dp = &model->pipe_plan(plan);
     const PipeModel& v = dp->view;
     // (the rest: launch_diag's own conditions, which every diagonal table built so far meets)
     if (v.sx || v.S == 0 || v.S > kDiagSetMaxSym || v.SM != 2 || v.wide || v.nrng == 0 || (size_t)v.nrng * 64 > v.P) return nullptr;
@@ -1887,7 +1856,7 @@ void Batch::begin_set_run(hipStream_t s, DiagSetEntry* e) {
     DeviceGuard g(model->device);
     const DevicePipePlan* dp = set_plan();
     if (!dp || !e) throw Error(SVH_E_STATE, "batch set: member is not planned on the diagonal plan");
-    pipe.ensure(nseq, dp->plan.nrng, s);
+    pipe.ensure(nseq, plan.scratch_G, s);
     pipe_ran = true;
     l2_ran = false;
     last_stream = s;
@@ -1919,117 +1888,80 @@ void Batch::run(uint32_t level, hipStream_t s) {
         fb.bp = d_bp.as<uint16_t>();
         fb.bp_off = p_bpoff;
     }
-    pipe_ran = false;
     l2_ran = false;
-    // (level >= 2: the chunks run elsewhere; the tail, rows resumed from the chunks' scores, runs on
-    // the diagonal plan when it has one for this batch -- the scratch then covers both plans)
-    const DevicePipePlan* dp = paths ? nullptr : model->diag_for(nseq);
-    if (dp && level <= 1) {  // diagonal plan: scratch
-        pipe.ensure(nseq, dp->plan.nrng, s);
+    // level <= 1: the plan of the load; level >= 2: the chunk route and the tail's plan as the model's
+    // _spec state stands now (spec_build may have run since the load)
+    const PassPlan pl = level <= 1 ? plan : model->resolve(nseq, false, level, true);
+    pipe_ran = on_scratch(pl.step);
+    if (pipe_ran) {
+        pipe.ensure(nseq, pl.scratch_G, s);
+        if (pipelined(pl.step)) pipe.note_launch(s);
         fb.pipe = &pipe.view;
-        pipe_ran = true;
-    } else if (const DevicePipePlan* pp = paths ? nullptr : model->pipe_for(nseq)) {  // pipelined plan: scratch
-        pipe.ensure(nseq, std::max<uint32_t>(pp->plan.G, dp ? dp->plan.nrng : 0u), s);
-        pipe.note_launch(s);
-        fb.pipe = &pipe.view;
-        pipe_ran = dp || model->band_for(false, nseq) != nullptr;  // launch_steps' condition
-    } else if (dp) {
-        pipe.ensure(nseq, dp->plan.nrng, s);
-        fb.pipe = &pipe.view;
-        pipe_ran = true;
     }
-    auto launch_step_kernel = [&](const FusedBatch& b, bool want_paths) { model->launch_steps(b, want_paths, s); };
 
     last_stream = s;
     if (timing) hip_check(hipEventRecord(ev_start, s), "hipEventRecord");
-    if (level <= 1 && pipe_paths) {
-        // decoded paths on the pipelined plan: its path variant, the chain path variant for rows
-        // whose speculation failed, the pipelined traceback (unflagged rows), the chain traceback
-        // (flagged rows)
-        const DevicePipePlan* ppl = model->pipe_paths_for(nseq);
-        const DeviceBandPlan* bpl = model->band_for(true);
-        if (!ppl || !bpl) throw Error(SVH_E_STATE, "batch planned for pipelined paths, model has no such plan");
-        pipe.ensure(nseq, ppl->plan.G, s);
-        pipe.note_launch(s);
+    if (level <= 1 && (pipe_paths || diag_paths)) {
+        // decoded paths on the pipelined or the diagonal plan, four launches: its path variant, the
+        // chain path variant for rows whose speculation failed, its traceback (unflagged rows), the
+        // chain traceback (flagged rows)
+        const DevicePipePlan& ppl = model->pipe_plan(pl);
+        const DeviceBandPlan& bpl = model->band;
+        FusedBatch cb = fb;  // chain buffers
+        cb.run_mask = pipe.view.viol;
+        cb.pipe = nullptr;
         FusedBatch pb = fb;
         pb.cmask = d_pmask.as<uint32_t>();
         pb.cmask_off = p_pmoff;
         pb.ckpt = d_pck.as<float>();
         pb.ckpt_off = p_pcoff;
-        pb.prec = d_prec.as<float2>();
+        pb.prec = d_prec.as<float2>();  // (diagonal: floats [nrng][len] per sequence, offsets in floats)
         pb.prec_off = p_proff;
         pb.fck = d_fck.as<float>();
         pb.fck_off = p_fcoff;
-        pb.pipe = &pipe.view;
-        if (ppl->plan.wide) hip_check(launch_pipew(ppl->view, pb, pipe.view, s), "wide pipelined Viterbi kernel (paths)");
-        else hip_check(launch_pipe(ppl->view, pb, pipe.view, s), "pipelined Viterbi kernel (paths)");
-        FusedBatch cb = fb;  // chain buffers
-        cb.run_mask = pipe.view.viol;
-        hip_check(launch_chain(bpl->view, 1, cb, s), "chain Viterbi kernel (pipe paths fallback)");
-        // SVH_PIPE_SKIP_TRACEBACK=1: diagnostic builds only (-DSVH_PIPE_DIAG; timing of the forward
-        // kernels alone, e.g. of an ablation build whose path records are not stored; the paths read
-        // back are wrong).  The production library has no such knob.
+        if (diag_paths) {
+            pb.hrec = d_dcc.as<uint32_t>();  // floats [nrng][checkpoints] per sequence
+            pb.hrec_off = p_dcoff;
+        }
+        hip_check(diag_paths       ? launch_diag(ppl.view, pb, pipe.view, s)
+                  : ppl.plan.wide ? launch_pipew(ppl.view, pb, pipe.view, s)
+                                  : launch_pipe(ppl.view, pb, pipe.view, s),
+                  "Viterbi kernel of the path plan");
+        hip_check(launch_chain(bpl.view, 1, cb, s), "chain Viterbi kernel (path plan fallback)");
+        // SVH_PIPE_SKIP_TRACEBACK=1: diagnostic builds only (-DSVH_PIPE_DIAG; timing of the pipelined
+        // forward kernels alone, e.g. of an ablation build whose path records are not stored; the
+        // paths read back are wrong).  The production library has no such knob.
 #ifdef SVH_PIPE_DIAG
-        static const bool skip_tb = std::getenv("SVH_PIPE_SKIP_TRACEBACK") && std::atoi(std::getenv("SVH_PIPE_SKIP_TRACEBACK"));
+        static const bool skip_env = std::getenv("SVH_PIPE_SKIP_TRACEBACK") && std::atoi(std::getenv("SVH_PIPE_SKIP_TRACEBACK"));
+        const bool skip_tb = skip_env && pipe_paths;
 #else
         constexpr bool skip_tb = false;
 #endif
         if (!skip_tb) {
-            hip_check(launch_pipe_traceback(ppl->view, pb, p_pathoff, d_paths.as<int32_t>(),
-                                            pipe.view.viol, s),
-                      "pipelined traceback kernel");
-            hip_check(launch_chain_traceback(bpl->view, cb, p_pathoff, d_paths.as<int32_t>(), s),
-                      "chain traceback kernel (pipe paths fallback)");
+            hip_check(diag_paths ? launch_diag_traceback(ppl.view, pb, p_pathoff, d_paths.as<int32_t>(), pipe.view.viol, s)
+                                 : launch_pipe_traceback(ppl.view, pb, p_pathoff, d_paths.as<int32_t>(), pipe.view.viol, s),
+                      "traceback kernel of the path plan");
+            hip_check(launch_chain_traceback(bpl.view, cb, p_pathoff, d_paths.as<int32_t>(), s),
+                      "chain traceback kernel (path plan fallback)");
         }
-        pipe_ran = true;
-    } else if (level <= 1 && diag_paths) {
-        // decoded paths on the diagonal plan: the same four launches -- its path variant, the chain
-        // path variant for rows whose speculation failed, the diagonal traceback (unflagged rows),
-        // the chain traceback (flagged rows)
-        const DevicePipePlan* dpl = model->diag_paths_for(nseq);
-        const DeviceBandPlan* bpl = model->band_for(true);
-        if (!dpl || !bpl) throw Error(SVH_E_STATE, "batch planned for diagonal paths, model has no such plan");
-        pipe.ensure(nseq, dpl->plan.nrng, s);
-        FusedBatch pb = fb;
-        pb.cmask = d_pmask.as<uint32_t>();
-        pb.cmask_off = p_pmoff;
-        pb.ckpt = d_pck.as<float>();
-        pb.ckpt_off = p_pcoff;
-        pb.prec = d_prec.as<float2>();  // floats [nrng][len] per sequence, offsets in floats
-        pb.prec_off = p_proff;
-        pb.fck = d_fck.as<float>();
-        pb.fck_off = p_fcoff;
-        pb.hrec = d_dcc.as<uint32_t>();  // floats [nrng][checkpoints] per sequence
-        pb.hrec_off = p_dcoff;
-        pb.pipe = &pipe.view;
-        hip_check(launch_diag(dpl->view, pb, pipe.view, s), "diagonal Viterbi kernel (paths)");
-        FusedBatch cb = fb;  // chain buffers
-        cb.run_mask = pipe.view.viol;
-        hip_check(launch_chain(bpl->view, 1, cb, s), "chain Viterbi kernel (diagonal paths fallback)");
-        hip_check(launch_diag_traceback(dpl->view, pb, p_pathoff, d_paths.as<int32_t>(), pipe.view.viol, s),
-                  "diagonal traceback kernel");
-        hip_check(launch_chain_traceback(bpl->view, cb, p_pathoff, d_paths.as<int32_t>(), s),
-                  "chain traceback kernel (diagonal paths fallback)");
-        pipe_ran = true;
     } else if (level <= 1) {
-        launch_step_kernel(fb, paths);
+        model->launch_steps(fb, pl, s);
         if (paths && chain_paths)
-            hip_check(launch_chain_traceback(model->band_for(true)->view, fb, p_pathoff,
-                                             d_paths.as<int32_t>(), s),
+            hip_check(launch_chain_traceback(model->band.view, fb, p_pathoff, d_paths.as<int32_t>(), s),
                       "chain traceback kernel");
         else if (paths)
             hip_check(launch_traceback(fb, p_pathoff, d_paths.as<int32_t>(), model->host.n, s),
                       "traceback kernel");
     } else {
         const uint32_t n = model->host.n;
-        const bool on_chip = level == 2 && model->spec2_on;
+        const bool on_chip = pl.chunks != ChunkRoute::Dense;  // level 2 on spec2.hip: no products
         // level 2 on the pipelined latency plan (pipe_l2.hip): every chunk of every row in one
         // launch into the second half of vbuf; rows whose speculation fails run again on spec2_kernel
         // from the first step's state (first half) into the second half; the tail reads row nseq + q
-        const bool l2pipe_on = on_chip && model->pipe_l2_on();
+        const bool l2pipe_on = pl.chunks == ChunkRoute::Spec2Pipe;
         // level 2 on the diagonal plan (diag_l2.hip), models created with SVH_KERNEL_DIAG: the same
         // buffers and the same re-run of flagged rows, the chunks' launch reads the first step's row q
-        const bool l2diag = on_chip && !l2pipe_on && model->diag_l2_on();
+        const bool l2diag = pl.chunks == ChunkRoute::Spec2Diag;
         const bool l2pipe = l2pipe_on || l2diag;  // (either: the chunks end in the second half, flags in d_l2viol)
         const uint32_t ready = level | (on_chip ? 0x100u : 0u) | (l2pipe_on ? 0x200u : 0u) | (l2diag ? 0x400u : 0u);
         if (spec_ready_level != ready) {
@@ -2052,8 +1984,8 @@ void Batch::run(uint32_t level, hipStream_t s) {
         float* vb = d_vbuf.as<float>();
         hip_check(launch_first_step(csr, fb.symbols, fb.sym_off, nseq, vb, s), "spec first step");
         if (l2diag) {
-            const DevicePipePlan& pl = model->pipe;
-            pipe.ensure(nseq, pl.plan.nrng, s);
+            const DevicePipePlan& lp = model->pipe;
+            pipe.ensure(nseq, lp.plan.nrng, s);
             PipeScratch x2 = pipe.view;
             x2.viol = d_l2viol.as<uint32_t>();  // its own flags: the tail's pass rewrites pipe.view.viol
             FusedBatch lb = fb;
@@ -2061,11 +1993,11 @@ void Batch::run(uint32_t level, hipStream_t s) {
             lb.scores = vb + (size_t)nseq * n;
             lb.best = nullptr;
             lb.pipe = nullptr;
-            hip_check(launch_diag_l2(pl.view, lb, x2, s), "diagonal level-2 kernel");
+            hip_check(launch_diag_l2(lp.view, lb, x2, s), "diagonal level-2 kernel");
             l2_ran = true;
         } else if (l2pipe) {
-            const DevicePipePlan& pl = model->pipe;
-            pipe.ensure(nseq, pl.plan.G, s);
+            const DevicePipePlan& lp = model->pipe;
+            pipe.ensure(nseq, lp.plan.G, s);
             pipe.note_launch(s);
             PipeScratch x2 = pipe.view;
             x2.viol = d_l2viol.as<uint32_t>();  // its own flags: the tail's pass rewrites pipe.view.viol
@@ -2073,7 +2005,7 @@ void Batch::run(uint32_t level, hipStream_t s) {
             lb.scores = vb + (size_t)nseq * n;
             lb.best = nullptr;
             lb.pipe = nullptr;
-            hip_check(launch_pipe_l2(pl.view, lb, x2, s), "pipelined level-2 kernel");
+            hip_check(launch_pipe_l2(lp.view, lb, x2, s), "pipelined level-2 kernel");
             l2_ran = true;
         }
         if (on_chip) {  // every chunk of every sequence in one launch, v in place (row q)
@@ -2113,7 +2045,7 @@ void Batch::run(uint32_t level, hipStream_t s) {
         tail.v_in_row = d_vrow.as<uint32_t>();
         tail.bp = nullptr;
         tail.bp_off = nullptr;
-        launch_step_kernel(tail, false);
+        model->launch_steps(tail, pl, s);
     }
     if (timing) hip_check(hipEventRecord(ev_stop, s), "hipEventRecord");
     ran = true;
@@ -2162,7 +2094,7 @@ void Batch::run_time_parallel(uint32_t seg, uint32_t probe, float tol, hipStream
     // basis rows: the heavy rows of the model's band plan (none for other models).  Every segment
     // runs nb guesses: the light guess (zeros, basis rows +inf), then a unit vector per basis row.
     TpBasis basis{};
-    if (const DeviceBandPlan* bpl = model->band_for(false))
+    if (const DeviceBandPlan* bpl = model->band_plan(model->resolve(0, false, 0, false)))
         for (int x = 0; x < kBandHeavy; ++x)
             if (bpl->plan.hvalid[x]) basis.hrow[basis.H++] = bpl->plan.hrow[x];
     const uint32_t nb = 1 + basis.H;
@@ -2239,7 +2171,7 @@ void Batch::run_time_parallel(uint32_t seg, uint32_t probe, float tol, hipStream
             fb.best = vbest;
             fb.fault = fault;
             fb.nseq = rows;
-            mdl->launch_steps(fb, false, s);
+            mdl->launch_steps(fb, mdl->resolve(rows, false, 0, false), s);  // (a view without scratch)
         });
     };
     // 1a: probes from the guesses, rows v * nb + b (segment 0: from the start column, and its
@@ -2434,55 +2366,63 @@ void Batch::read_async(hipStream_t s, float* scores, int64_t* best, int32_t* pat
         hip_check(hipMemcpyAsync(paths_out, d_paths.ptr, (size_t)total * 4, hipMemcpyDeviceToHost, s), "paths D2H");
 }
 
-// One pass of the per-observation step kernel over a batch view (steps begin..end-1 of each row).
-void Model::launch_steps(const FusedBatch& b, bool want_paths, hipStream_t s) const {
-    const DevicePlan* dp = plan_for(want_paths);
-    const DeviceBandPlan* bpl = band_for(want_paths, b.nseq);
-    const DevicePipePlan* dpl = want_paths ? nullptr : diag_for(b.nseq);
-    if (dpl && b.pipe && b.pipe->rows >= b.nseq && b.pipe->G >= dpl->plan.nrng) {
-        // diagonal plan: rows whose speculation fails are re-run in the same launch
-        hip_check(launch_diag(dpl->view, b, *b.pipe, s), "diagonal Viterbi kernel");
-        return;
-    }
-    const DevicePipePlan* ppl = want_paths ? nullptr : pipe_for(b.nseq);
-    if (ppl && bpl && b.pipe && b.pipe->rows >= b.nseq && b.pipe->G >= ppl->plan.G) {
-        if (ppl->plan.wide) hip_check(launch_pipew(ppl->view, b, *b.pipe, s), "wide pipelined Viterbi kernel");
-        else hip_check(launch_pipe(ppl->view, b, *b.pipe, s), "pipelined Viterbi kernel");
-        if (ppl->view.stamps && !ppl->plan.wide) {
-            hip_check(hipStreamSynchronize(s), "stamps");
-            ppl->report_stamps(b.nseq);
-        }
-        // rows whose speculation failed: the latency plan re-runs them itself (PipeModel::rerun:
-        // no second launch on the common path); otherwise they run again on the serial chain
-        // kernel (the others exit);
-        // SVH_PIPE_SKIP_FALLBACK=1: diagnostic builds only (-DSVH_PIPE_DIAG; timing without the
-        // second launch; results of flagged rows would be wrong)
+// One pass of the per-observation step kernel of `pl` over a batch view (steps begin..end-1 of each
+// row).  Nothing is decided here; a plan on scratch only has what the resolver was told checked.
+void Model::launch_steps(const FusedBatch& b, const PassPlan& pl, hipStream_t s) const {
+    const bool want_paths = pl.records != PathRecords::None;
+    if (on_scratch(pl.step) && !(b.pipe && b.pipe->rows >= b.nseq && b.pipe->G >= pl.scratch_G))
+        throw Error(SVH_E_STATE, "step kernel planned on pipelined scratch the view does not bring");
+    const DeviceBandPlan* bpl = band_plan(pl);
+    const int ha = bpl ? (int)std::max<uint32_t>(bpl->plan.HA, 1) : 0;
+    switch (pl.step) {
+        case StepKernel::Diag:  // rows whose speculation fails are re-run in the same launch
+            hip_check(launch_diag(pipe.view, b, *b.pipe, s), "diagonal Viterbi kernel");
+            return;
+        case StepKernel::Pipe:
+        case StepKernel::PipeWide: {
+            const DevicePipePlan& ppl = pipe_plan(pl);
+            if (ppl.plan.wide) hip_check(launch_pipew(ppl.view, b, *b.pipe, s), "wide pipelined Viterbi kernel");
+            else hip_check(launch_pipe(ppl.view, b, *b.pipe, s), "pipelined Viterbi kernel");
+            if (ppl.view.stamps && !ppl.plan.wide) {
+                hip_check(hipStreamSynchronize(s), "stamps");
+                ppl.report_stamps(b.nseq);
+            }
+            // rows whose speculation failed: the latency plan re-runs them itself (PipeModel::rerun:
+            // no second launch on the common path); otherwise they run again on the serial chain
+            // kernel (the others exit);
+            // SVH_PIPE_SKIP_FALLBACK=1: diagnostic builds only (-DSVH_PIPE_DIAG; timing without the
+            // second launch; results of flagged rows would be wrong)
 #ifdef SVH_PIPE_DIAG
-        static const bool skip_fb = std::getenv("SVH_PIPE_SKIP_FALLBACK") && std::atoi(std::getenv("SVH_PIPE_SKIP_FALLBACK"));
-        if (skip_fb) return;
+            static const bool skip_fb = std::getenv("SVH_PIPE_SKIP_FALLBACK") && std::atoi(std::getenv("SVH_PIPE_SKIP_FALLBACK"));
+            if (skip_fb) return;
 #endif
-        if (!ppl->plan.wide && ppl->view.rerun) return;
-        FusedBatch fb = b;
-        fb.run_mask = b.pipe->viol;
-        fb.pipe = nullptr;
-        const int ha = (int)std::max<uint32_t>(bpl->plan.HA, 1);
-        if (bpl->plan.chain) hip_check(launch_chain(bpl->view, ha, fb, s), "chain Viterbi kernel (pipe fallback)");
-        else hip_check(launch_band(bpl->view, ha, fb, s), "band Viterbi kernel (pipe fallback)");
-        return;
-    }
-    if (bpl) {
-        const int ha = (int)std::max<uint32_t>(bpl->plan.HA, 1);
-        if (bpl->plan.chain) hip_check(launch_chain(bpl->view, ha, b, s), "chain Viterbi kernel");
-        else hip_check(launch_band(bpl->view, ha, b, s), "band Viterbi kernel");
-        if (bpl->view.dbg & (4u | 128u)) {
-            hip_check(hipStreamSynchronize(s), "stamps");
-            bpl->report_stamps(b.nseq);
+            if (!pl.serial_fallback) return;
+            FusedBatch fb = b;
+            fb.run_mask = b.pipe->viol;
+            fb.pipe = nullptr;
+            if (bpl->plan.chain) hip_check(launch_chain(bpl->view, ha, fb, s), "chain Viterbi kernel (pipe fallback)");
+            else hip_check(launch_band(bpl->view, ha, fb, s), "band Viterbi kernel (pipe fallback)");
+            return;
         }
-    } else if (dp) {
-        hip_check(launch_fused(dp->view, b, dp->plan.family, want_paths, s), "fused Viterbi kernel");
-    } else {
-        const uint32_t threads = std::min<uint32_t>(1024, ((host.n + 63) / 64) * 64);
-        hip_check(launch_generic(csr_view(), b, (int)threads, want_paths, s), "generic Viterbi kernel");
+        case StepKernel::Chain:
+        case StepKernel::Band:
+            if (bpl->plan.chain) hip_check(launch_chain(bpl->view, ha, b, s), "chain Viterbi kernel");
+            else hip_check(launch_band(bpl->view, ha, b, s), "band Viterbi kernel");
+            if (bpl->view.dbg & (4u | 128u)) {
+                hip_check(hipStreamSynchronize(s), "stamps");
+                bpl->report_stamps(b.nseq);
+            }
+            return;
+        case StepKernel::Fused: {
+            const DevicePlan* dp = fused_plan(want_paths);
+            hip_check(launch_fused(dp->view, b, dp->plan.family, want_paths, s), "fused Viterbi kernel");
+            return;
+        }
+        case StepKernel::Generic: {
+            const uint32_t threads = std::min<uint32_t>(1024, ((host.n + 63) / 64) * 64);
+            hip_check(launch_generic(csr_view(), b, (int)threads, want_paths, s), "generic Viterbi kernel");
+            return;
+        }
     }
 }
 
@@ -2535,32 +2475,28 @@ float Batch::step_floor_ms(hipStream_t s, uint32_t reps) {
     std::lock_guard<std::mutex> lock(model->mu);
     DeviceGuard g(model->device);
     if (!s) s = model->stream;
-    const DevicePipePlan* pp = model->pipe_for(nseq);
     // a batch whose scores pass runs the diagonal plan: that plan's floor -- its loader-wave launch
     // with the loader wave idle, no LDS reads in the steps and no partials, arrival count, combine or
     // re-run (diag.hip FL, dld = 3), i.e. the prologue and the steps' arithmetic alone; every other
-    // batch: the latency plan's
-    const DevicePipePlan* dp = paths ? nullptr : model->diag_for(nseq);
+    // batch: the latency plan's, if the scores pass of this many rows runs it
+    const PassPlan sp = model->resolve(nseq, false, 0, true);
+    const DevicePipePlan* dp = !paths && sp.step == StepKernel::Diag ? &model->pipe : nullptr;
     PipeModel dview{};
     if (dp) {
         dview = dp->view;
         dview.dld = 3;
         if (!diag_loader_for(dview, nseq, false, false)) dp = nullptr;
     }
-    if (!dp && (!pp || pp->plan.wide || pp->view.tm != 4 || pp->plan.W != 4 || !model->band_for(false, nseq)))
+    const DevicePipePlan* pp = sp.no_diag == StepKernel::Pipe ? &model->pipe : nullptr;
+    if (!dp && (!pp || pp->view.tm != 4 || pp->plan.W != 4))
         throw Error(SVH_E_UNSUPPORTED, "step floor: the batch's plan is neither the diagonal plan nor the pipelined latency plan (TM 4)");
     floor_scratch.ensure(nseq, dp ? std::max(dp->plan.nrng, dp->plan.nrng2) : pp->plan.G, s);
     const size_t n = model->host.n;
     d_floor_out.reserve(16 + (size_t)nseq * n * 4);
-    FusedBatch fb;
-    std::memset(&fb, 0, sizeof(fb));
-    fb.symbols = p_sym;
-    fb.sym_off = p_symoff;
-    fb.begin = p_begin;
-    fb.end = p_end;
+    FusedBatch fb = scores_view();  // this batch's inputs, outputs of the floor's own
+    fb.best = nullptr;
     fb.fault = d_floor_out.as<uint32_t>();
     fb.scores = reinterpret_cast<float*>(d_floor_out.as<uint8_t>() + 16);
-    fb.nseq = nseq;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hip_check(hipEventCreate(&e0), "hipEventCreate");
     hip_check(hipEventCreate(&e1), "hipEventCreate");

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "dispatch.h"
 #include "error.h"
 #include "kernels.h"
 #include "set_table.h"
@@ -226,7 +227,7 @@ struct PipeScratchBuffers {
 struct Model {
     std::mutex mu;
     int device = 0;
-    int kernel_pref = SVH_KERNEL_AUTO;
+    ModelCaps caps;  // what this model can run (dispatch.h): filled once by the constructor
     HostModel host;
     hipStream_t stream = nullptr;
     DeviceBandPlan band;             // chain kernel plan (scores-only runs of MSV-shaped models)
@@ -234,13 +235,7 @@ struct Model {
                                      // 4 waves (more workgroups per CU), scores only
     uint32_t cu_count = 0;
     DevicePipePlan pipe;             // pipelined chain plan (latency path for small batches)
-    uint32_t pipe_max_nseq = 0;      // AUTO: pipelined plan for scores-only batches of at most this many rows
-    uint32_t pipe_max_nseq_paths = 0;  // ... for decoded-path batches
-    uint32_t diag_max_nseq = 0;      // AUTO: the diagonal plan (diag.hip) for scores-only batches of at most this many rows
-    // diagonal plan for a scores-only pass over nseq rows from observation 0 (nullptr: none)
-    const DevicePipePlan* diag_for(uint32_t nseq) const;
     DevicePipePlan pipe_wide;        // wide pipelined plan (throughput path for batches that fill the chip)
-    uint32_t pipew_min_nseq = 0;     // AUTO: wide pipelined plan for batches of at least this many rows
     DevicePlan fast_plan;            // fastest fused plan (may use uniform heavy rows)
     DevicePlan paths_plan_storage;   // term-by-term plan when fast_plan is uniform
     const DevicePlan* paths_plan = nullptr;
@@ -252,41 +247,32 @@ struct Model {
     // _spec level 2 on chip (spec2.hip): built by spec_build(2) unless SVH_SPEC_DENSE=1
     DeviceSpec2Plan spec2;
     bool spec2_on = false;
-    // level 2 runs on the pipelined latency plan (pipe_l2.hip) with spec2_kernel as its exact
-    // fallback: the model has both, every score >= 0, and the kernel preference allows the pipe
-    bool pipe_l2_on() const;
-    // level 2 runs on the diagonal plan (diag_l2.hip) with spec2_kernel as its exact fallback: the
-    // model was created with SVH_KERNEL_DIAG and has the on-chip plan and the diagonal table, every
-    // score is >= 0, at most 32 symbols, S takes no term from F and two workgroups fit a CU's LDS
-    bool diag_l2_on() const;
     bool spec_dense = false;  // svh_model_opts.flags & SVH_MODEL_SPEC_DENSE
 
     Model(const HostModel& h, const svh_model_opts* opts);
     ~Model();
     CsrModel csr_view() const;
-    // Fused plan to run (nullptr: generic kernel).
-    const DevicePlan* plan_for(bool paths) const;
-    // Chain plan to run for a pass over nseq sequences (nullptr: use plan_for(paths)).
-    const DeviceBandPlan* band_for(bool paths, uint32_t nseq = 0) const;
-    // Pipelined plan for a scores-only pass over nseq rows (nullptr: none).
-    const DevicePipePlan* pipe_for(uint32_t nseq) const;
-    // Pipelined plan for a decoded-path pass over nseq rows (nullptr: the chain / fused variant):
-    // the latency plan, with the chain kernel's path variant as the fallback of flagged rows.
-    const DevicePipePlan* pipe_paths_for(uint32_t nseq) const;
-    // Diagonal plan for a decoded-path pass (diag.hip PATHS, nullptr: none): only for models created
-    // with SVH_KERNEL_DIAG whose F wins every tie and feeds no term to S, whose walk fits the traceback's LDS and whose path
-    // variant keeps two workgroups per CU; the chain path variant is the fallback of flagged rows.
-    const DevicePipePlan* diag_paths_for(uint32_t nseq) const;
+    // The kernels of a pass over `rows` rows at `level` (dispatch.h resolve_pass on this model's
+    // caps and its current _spec state); scratch: the view brings pipelined scratch.
+    PassPlan resolve(uint32_t rows, bool paths, uint32_t level, bool scratch) const;
+    // The plan objects a PassPlan names: the chain plan of the pass (nullptr: fused / generic), its
+    // pipelined plan (step Pipe, PipeWide or Diag) and its fused plan (nullptr: generic kernel).
+    const DeviceBandPlan* band_plan(const PassPlan& p) const;
+    const DevicePipePlan& pipe_plan(const PassPlan& p) const { return p.step == StepKernel::PipeWide ? pipe_wide : pipe; }
+    const DevicePlan* fused_plan(bool paths) const;
     void spec_build(uint32_t level, hipStream_t s);
     svh_model_info info(uint32_t nseq = 0, bool paths = false, uint32_t level = 0) const;
-    // one pass of the step kernel the model plans for (chain, band, fused or generic)
-    void launch_steps(const FusedBatch& b, bool paths, hipStream_t s) const;
+    // one pass of the step kernel of `p` over a batch view
+    void launch_steps(const FusedBatch& b, const PassPlan& p, hipStream_t s) const;
 };
 
 struct Batch {
     Model* model;
     uint32_t nseq = 0;
     bool paths = false;
+    // the level <= 1 pass of the sequences loaded last (Model::resolve); chain_paths / pipe_paths /
+    // diag_paths below are copies of its records, set by load()
+    PassPlan plan;
     std::vector<uint64_t> offsets;  // host copy of the caller's prefix offsets
     std::vector<uint32_t> lens;
     uint64_t total = 0;
