@@ -26,7 +26,7 @@ HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 
 CPP_TESTS := tests/cpp/test_HIP_impl tests/cpp/test_HIP_spec_impl tests/cpp/test_semantic_equality \
              tests/cpp/test_readers_asan tests/cpp/test_host_asan tests/cpp/test_diag_sizes_asan \
-             tests/cpp/test_set_table tests/cpp/test_dispatch
+             tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4
 
 .PHONY: all lib oracle ref tests tools clean
 all: lib oracle tests tools ref
@@ -87,6 +87,14 @@ $(BUILD)/asan/test_host_asan.o: tests/cpp/test_host_asan.cpp $(HDRS) | $(BUILD)
 	mkdir -p $(BUILD)/asan
 	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -c $< -o $@
 tests/cpp/test_host_asan: $(BUILD)/asan/test_host_asan.o $(ASAN_OBJS) $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS))
+	$(HIPCC) --offload-arch=$(ARCH) $(ASAN_HOST) -o $@ $^
+
+# The diagonal plan's quad table against its plane table (runtime.cpp make_pipe_plan) under the same
+# sanitizers, linked as test_host_asan is; the test touches no GPU.
+$(BUILD)/asan/test_dtab4.o: tests/cpp/test_dtab4.cpp $(HDRS) | $(BUILD)
+	mkdir -p $(BUILD)/asan
+	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -c $< -o $@
+tests/cpp/test_dtab4: $(BUILD)/asan/test_dtab4.o $(ASAN_OBJS) $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS))
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN_HOST) -o $@ $^
 
 # The diagonal path variant's record sizes and offsets (kernels.h) under the same sanitizers: one

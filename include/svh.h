@@ -246,6 +246,13 @@ int svh_batch_step_floor_ms(svh_batch_t b, void* stream, uint32_t reps, float* m
 /* The plan svh_batch_run(level) launches for this batch (its sequence count and paths flag
  * decide between the narrow and the wide chain plan): kernel/threads/slots of the model info. */
 int svh_batch_plan(svh_batch_t b, uint32_t level, svh_model_info* info);
+/* The quad ring of that plan's diagonal launch.  A scores launch of two diagonals per lane with the
+ * loader wave (svh_model_info.diag_sm) keeps every ring column as the 16 bytes a lane's two diagonals
+ * read in one step, where that wider ring fits the CU's LDS: *quad = 1 and *lds_bytes = the launch's LDS
+ * per workgroup (svh_batch_plan's lds_bytes stays the plane layout's); else 0 and 0.  The environment
+ * variable SVH_DIAG_QUAD = 0 / 1, read when a model is created, forces it off, or on wherever eligible.
+ * (A call of its own, not a field of svh_model_info: that struct and SVH_ABI_VERSION stay as they are.) */
+int svh_batch_diag_quad(svh_batch_t b, uint32_t level, int32_t* quad, uint64_t* lds_bytes);
 /* Rows of the last run whose pipelined pass (SVH_KERNEL_PIPE, _PIPE_WIDE, _SPEC2_PIPE, _SPEC2_DIAG) failed its
  * speculation check and were re-run exactly (in the same launch, by the serial chain kernel, or at
  * level 2 by the on-chip chunk kernel; results are identical either way); 0 if the last run did

@@ -109,6 +109,7 @@ SIGNATURES = {
     "svh_batch_fallback_rows": (c_int, [c_void_p, P_u32]),
     "svh_batch_plan": (c_int, [c_void_p, c_uint32, POINTER(svh_model_info)]),
     "svh_batch_fallbacks": (c_int, [c_void_p, P_u64]),
+    "svh_batch_diag_quad": (c_int, [c_void_p, c_uint32, POINTER(c_int32), P_u64]),
     "svh_pipe_variant_built": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, POINTER(ctypes.c_int32)]),
     "svh_batch_debug_fault": (c_int, [c_void_p, c_void_p]),
     "svh_batch_destroy": (c_int, [c_void_p]),

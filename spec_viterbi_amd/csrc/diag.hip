@@ -117,6 +117,11 @@ static_assert(kDMaxSym == kDiagSetMaxSym, "kernels.h: what the runtime admits to
 #ifndef SVH_DIAG_LDDRAIN
 #define SVH_DIAG_LDDRAIN 1
 #endif
+// SVH_DIAG_QDMA (A/B of the quad ring's refill): 1 = one LDS-DMA instruction per symbol and group
+// (global_load_lds_dwordx4), 0 = a global load into registers and a 16-byte LDS write per symbol
+#ifndef SVH_DIAG_QDMA
+#define SVH_DIAG_QDMA 1
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif
@@ -126,6 +131,10 @@ __device__ __forceinline__ f2 lds_ld2(uint32_t a) {
 }
 __device__ __forceinline__ float lds_ld1(uint32_t a) {
     return *(const __attribute__((address_space(3))) float*)(size_t)a;
+}
+typedef float f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f4 lds_ld4(uint32_t a) {
+    return *(const __attribute__((address_space(3))) f4*)(size_t)a;
 }
 
 // The speculation check, one VALU: EXEC &= !(a < b) (v_cmpx writes VCC and EXEC).  A lane whose
@@ -154,11 +163,12 @@ __device__ __forceinline__ void exec_collect(uint64_t& alive) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1, bool ld = false) {
-    // ring [S][kDRS] float2 (dm = 2: [S][2][kDRS2] floats) | symbol template [S][8] | constants [W][2][kDK][kDE] |
-    // ring addresses [W][2][kDK] | X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
+__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1, bool ld = false,
+                                                   bool quad = false) {
+    // ring [S][kDRS] float2 (dm = 2: [S][2][kDRS2] floats; quad: [S][kDRS] float4) | symbol template [S][8] |
+    // constants [W][2][kDK][kDE] | ring addresses [W][2][kDK] | X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
     // (ld, the loader-wave variant: three stream buffers instead of two)
-    return ((size_t)S * (dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * (ld ? 3 : 2) * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
+    return ((size_t)S * (quad ? kDRS * 2 : dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * (ld ? 3 : 2) * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
 }
 
 // Decoded paths (PATHS; the walk is pipe_paths.hip's diag entry): fold ring [W][kFS][64] floats behind
@@ -201,8 +211,16 @@ __host__ __device__ constexpr size_t diag_lds_paths(uint32_t W, uint32_t S, bool
 // work-group have already terminated, this waits on only the surviving waves" (AMD Instinct CDNA3 /
 // CDNA4 ISA reference guides, SOPP instructions).
 //
+// QD (DM = 2 with LD, scores only): the quad ring.  Ring column u holds the four table values a lane
+// needs of a step as one 16-byte entry {ea[c], ea[c + 64], eb[c], eb[c + 64]} (c = the column's table
+// position, + 64 modulo NP: PipeModel::dtab4 holds them so), [S][kDRS] float4 -- the one-diagonal
+// kernel's geometry again, five groups of 64 columns and a mirror of the first 64, three groups in use
+// per block -- so a step's table read is one ds_read_b128 whose registers are the two aligned pairs
+// the packed adds take, and a symbol's group is 1 KiB contiguous in the table and in the ring: the
+// loader wave refills it with one global_load_lds_dwordx4 (diag_body.h, "Quad ring timing").
+//
 // The body is diag_body.h, included here and in diag_set_kernel below.
-template <int W, bool SX, bool PATHS = false, int DM = 1, bool LD = false, bool FL = false>
+template <int W, bool SX, bool PATHS = false, int DM = 1, bool LD = false, bool FL = false, bool QD = false>
 __global__ __launch_bounds__(64 * (W + (LD ? 1 : 0))) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     const uint32_t bx = blockIdx.x;
@@ -237,7 +255,7 @@ __device__ __forceinline__ void in_global(T*&... p) {
 template <int W>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_set_kernel(const DiagSetEntry* __restrict__ e, const uint32_t* __restrict__ first, uint32_t ne) {
-    constexpr bool SX = false, PATHS = false, LD = false, FL = false;
+    constexpr bool SX = false, PATHS = false, LD = false, FL = false, QD = false;
     constexpr int DM = 1;
     const uint32_t lane = threadIdx.x & 63u, gbx = blockIdx.x;
     uint32_t cnt = 0;
@@ -252,7 +270,8 @@ void diag_set_kernel(const DiagSetEntry* __restrict__ e, const uint32_t* __restr
     const uint32_t i = (uint32_t)uniform((int)(cnt - 1));
     const uint32_t f0 = first[i];
     DiagSetEntry ent = e[i];
-    in_global(ent.m.tab, ent.m.e0, ent.m.start, ent.m.lrow, ent.m.hc, ent.m.dtab, ent.m.pflags, ent.m.spos, ent.m.stamps, ent.m.dtab2);
+    in_global(ent.m.tab, ent.m.e0, ent.m.start, ent.m.lrow, ent.m.hc, ent.m.dtab, ent.m.pflags, ent.m.spos, ent.m.stamps, ent.m.dtab2,
+              ent.m.dtab4);
     in_global(ent.b.symbols, ent.b.sym_off, ent.b.begin, ent.b.end, ent.b.v_in, ent.b.v_in_row, ent.b.scores, ent.b.best,
               ent.b.run_mask, ent.b.fault);
     in_global(ent.x.ctr, ent.x.done, ent.x.part, ent.x.gran, ent.x.cons, ent.x.viol, ent.x.xcc);
@@ -315,6 +334,15 @@ const void* diag_loader_ptr(bool sx) {
                   : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM, true>);
     }
 }
+template <int W>
+const void* diag_quad_ptr(bool sx) {
+    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || kDK != 64) {
+        return nullptr;
+    } else {
+        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, 2, true, false, true>)
+                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, 2, true, false, true>);
+    }
+}
 // (Only the instantiations without X_SF: with both PATHS and SX the block's body is past the
 // compiler's limit for `#pragma unroll`, the 64 steps are then unrolled in part, the register
 // vectors indexed at run time, and the kernel is some 600 instructions per step.  Models whose S
@@ -339,14 +367,16 @@ const void* diag_paths_ptr() {
 
 uint32_t diag_waves_for(uint64_t nseq) { return nseq >= 4 ? 4u : nseq >= 2 ? 2u : 1u; }
 
-static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1, bool ld = false) {
+static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1, bool ld = false, bool quad = false) {
     const size_t rerun = (2 * (size_t)P + 2 * W) * 4;  // pipe_rerun_row: v[2][P], red[2][W]
-    const size_t mainb = diag_lds_main(W, S, sx, dm, ld);
+    const size_t mainb = diag_lds_main(W, S, sx, dm, ld, quad);
     return mainb > rerun ? mainb : rerun;
 }
 
 // (the larger of the two kernels': models that use X_SF keep one stream more)
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm, bool ld) { return diag_lds(W, S, P, true, dm, ld); }
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm, bool ld, bool quad) {
+    return diag_lds(W, S, P, true, dm, ld, quad);
+}
 
 uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
     if (paths || !m.dtab2 || !m.nrng2 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) return 1;
@@ -366,6 +396,16 @@ bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths
     // a wave alone on its SIMD has no neighbour to hide the block's other work behind, and the third
     // stream buffer costs no residency: launches of at most one workgroup per CU
     return m.cus && (nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng) <= m.cus;
+}
+
+bool diag_quad_table_fits(uint32_t S, uint32_t P, bool sx) {
+    return SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0 && kDK == 64 && diag_lds(1, S, P, sx, 2, true, true) <= 160 * 1024;
+}
+
+bool diag_quad_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
+    if (!m.dtab4 || m.dqd == 1 || m.dld == 3 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || kDK != 64) return false;
+    if (diag_sm_for(m, nseq, resumed, paths) != 2 || !diag_loader_for(m, nseq, resumed, paths)) return false;
+    return diag_lds(diag_waves_for(nseq), m.S, m.P, m.sx != 0, 2, true, true) <= 160 * 1024;
 }
 
 size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx) { return diag_lds_paths(W, S, sx); }
@@ -394,14 +434,16 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     if (dm == 2 && ((size_t)m.nrng2 * 128 != m.P || x.G < m.nrng2)) return hipErrorInvalidValue;
     const bool sx = m.sx != 0;
     const bool ld = diag_loader_for(m, b.nseq, b.v_in != nullptr, paths);
+    const bool quad = diag_quad_for(m, b.nseq, b.v_in != nullptr, paths);
     const void* fn = paths     ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
                      : ld && m.dld == 3 ? (dm == 2 ? diag_floor_ptr<2>(sx) : diag_floor_ptr<1>(sx))
+                     : quad    ? (W == 4 ? diag_quad_ptr<4>(sx) : W == 2 ? diag_quad_ptr<2>(sx) : diag_quad_ptr<1>(sx))
                      : ld      ? (dm == 2 ? (W == 4 ? diag_loader_ptr<4, 2>(sx) : W == 2 ? diag_loader_ptr<2, 2>(sx) : diag_loader_ptr<1, 2>(sx))
                                           : (W == 4 ? diag_loader_ptr<4, 1>(sx) : W == 2 ? diag_loader_ptr<2, 1>(sx) : diag_loader_ptr<1, 1>(sx)))
                      : dm == 2 ? (W == 4 ? diag_ptr<4, 2>(sx) : W == 2 ? diag_ptr<2, 2>(sx) : diag_ptr<1, 2>(sx))
                                : (W == 4 ? diag_ptr<4>(sx) : W == 2 ? diag_ptr<2>(sx) : diag_ptr<1>(sx));
-    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm, ld);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm, ld, quad);
+    if (lds > 160 * 1024 || !fn) return hipErrorInvalidValue;
     const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng);
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     // even placement: a launch that fits the chip gets its LDS request raised so that no CU can take

@@ -1,5 +1,5 @@
 // The body of the diagonal plan's kernels (diag.hip), included inside a kernel: one workgroup's whole
-// pass.  In scope where it is included: the template parameters W, SX, PATHS, DM, LD, FL (as constants
+// pass.  In scope where it is included: the template parameters W, SX, PATHS, DM, LD, FL, QD (as constants
 // where the kernel fixes them), the launch's `m` (PipeModel), `b` (FusedBatch), `x` (PipeScratch) and
 // `bx`, the workgroup's index within that launch's grid (rg = bx % NR, grp = bx / NR).
 // diag_viterbi_kernel has its arguments and blockIdx.x there; diag_set_kernel the triple and the local
@@ -10,12 +10,14 @@
     static_assert(DM == 1 || (DM == 2 && !PATHS), "decoded paths keep one diagonal per lane");
     static_assert(!LD || (!PATHS && SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0), "the loader wave: scores only");
     static_assert(!FL || LD, "the floor is a loader-wave launch");
+    static_assert(!QD || (DM == 2 && LD && !PATHS && !FL && kDK == 64),
+                  "the quad ring: two diagonals per lane, the loader wave, scores only; a group is one wave's 64 x 16 bytes");
     constexpr uint32_t NB = LD ? 3 : 2;                  // stream buffers per wave
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr uint32_t RW = 64 * DM;                     // diagonals (positions) per range
-    constexpr uint32_t RS = DM == 2 ? kDRS2 : kDRS;      // pairs of floats per symbol in the ring
+    constexpr uint32_t RS = QD ? kDRS * 2 : DM == 2 ? kDRS2 : kDRS;  // pairs of floats per symbol in the ring
     const uint32_t S = m.S, NR = DM == 2 ? m.nrng2 : m.nrng, NP = NR * RW, P = m.P;
-    float* ring = lds;                                   // [S][kDRS] {ea, eb}; DM = 2: [S][2][kDRS2]
+    float* ring = lds;                                   // [S][kDRS] {ea, eb}; DM = 2: [S][2][kDRS2]; QD: [S][kDRS] quads
     float* hcr = ring + (size_t)S * RS * 2;              // [S][8] stream template of symbol o
     float* strm = hcr + S * 8;                           // [W][NB][kDK] {A_F, A_S, X_FF, X_SS}
     float* adr = strm + W * NB * kDK * kDE;              // [W][NB][kDK] ring address of (o_t, step)
@@ -172,7 +174,7 @@
     auto sbuildl = [&](uint32_t kb) {
         if (lane < kDK) {
             const uint32_t i = kb * kDK + 1 + lane;
-            const uint32_t ro = (i % kDR) * (DM == 2 ? 4u : 8u);
+            const uint32_t ro = (i % kDR) * (QD ? 16u : DM == 2 ? 4u : 8u);
             const uint32_t e0 = (kb % NB) * kDK + lane;
 #pragma unroll
             for (int u = 0; u < W; ++u) {
@@ -183,6 +185,42 @@
                 *reinterpret_cast<float4*>(strm + e * kDE) = h0;
                 adr[e] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, h1.y) + ro);
                 if (SX) xsf[e] = h1.x;
+            }
+        }
+    };
+    // ---- the quad ring's refill (QD): group g of symbol o is 64 quads, 1 KiB contiguous in dtab4 (from
+    // column c0 of the symbol's row) and in the ring (from slot s0 of the symbol's plane): one LDS-DMA
+    // wave-instruction, lane l's 16 bytes from dtab4[o][c0 + l] to the wave-uniform base + 16 l; a group
+    // that is the ring's first goes into the mirror behind the ring as well.  Wave wv of nw takes the
+    // symbols o = wv, wv + nw, ...  Not waited for here.
+    // (SVH_DIAG_QDMA = 0, the A/B: through registers, global_load_dwordx4 and ds_write_b128.)
+    auto qfill = [&](uint32_t g, uint32_t wv, uint32_t nw) {
+        if constexpr (QD) {
+            const uint32_t c0 = (rg * RW + g * kDK) % NP;
+            const uint32_t s0 = (g % kDG) * kDK;
+            const float4* src = m.dtab4 + c0 + lane;
+            if constexpr (SVH_DIAG_QDMA) {
+                for (uint32_t o = wv; o < S; o += nw) {
+                    const uint32_t d = ring_a + (o * kDRS + s0) * 16u;
+                    lds_dma16(src + (size_t)o * NP, d);
+                    if (s0 == 0) lds_dma16(src + (size_t)o * NP, d + kDR * 16u);
+                }
+            } else {
+                constexpr uint32_t kQB = 8;  // symbols per batch of loads
+                for (uint32_t o0 = wv; o0 < S; o0 += nw * kQB) {
+                    float4 v[kQB];
+#pragma unroll
+                    for (uint32_t r = 0; r < kQB; ++r) v[r] = src[(size_t)min(o0 + r * nw, S - 1) * NP];
+#pragma unroll
+                    for (uint32_t r = 0; r < kQB; ++r) {
+                        const uint32_t o = o0 + r * nw;
+                        if (o < S) {
+                            float* d = ring + ((size_t)o * kDRS + s0 + lane) * 4;
+                            *reinterpret_cast<float4*>(d) = v[r];
+                            if (s0 == 0) *reinterpret_cast<float4*>(d + kDR * 4) = v[r];
+                        }
+                    }
+                }
             }
         }
     };
@@ -207,7 +245,20 @@
     if constexpr (LD) {
         // the step waves fill groups 0..3; the loader wave: group 4 in flight, the streams of blocks
         // 0 and 1 (behind the barrier: they need the symbol template), the symbols of block 2
-        if (ldr) {
+        if constexpr (QD) {
+            // the step waves fill groups 0..3 (the loader wave's first is group 4, during block 0); all
+            // of it has landed (vmcnt(0)) in the issuing wave ahead of the first of the two barriers
+            // before the first ring read
+            if (ldr) {
+                symloadl(0);
+            } else {
+                qfill(0, w, W);
+                qfill(1, w, W);
+                qfill(2, w, W);
+                qfill(3, w, W);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if (ldr) {
             gloadl(4);
             symloadl(0);
         } else {
@@ -343,6 +394,14 @@
         // (the element copied to a scalar first: __builtin_bit_cast of an ext-vector element lvalue
         // reads the vector's first element)
         const float roff = aq[j % (2 * kAG)];
+        if constexpr (QD) {  // {ea_a, ea_b, eb_a, eb_b}: one 16-byte read
+            const f4 e = lds_ld4(__builtin_bit_cast(uint32_t, roff) + lane * 16u);
+            eq[4 * (j % kNE)] = e.x;
+            eq[4 * (j % kNE) + 1] = e.y;
+            eq[4 * (j % kNE) + 2] = e.z;
+            eq[4 * (j % kNE) + 3] = e.w;
+            return;
+        }
         if constexpr (DM == 2) {  // {ea_a, ea_b}, {eb_a, eb_b}: one two-address read per plane
             const uint32_t a = __builtin_bit_cast(uint32_t, roff) + lane * 4u;
             eq[4 * (j % kNE)] = lds_ld1(a);
@@ -518,8 +577,8 @@
                 }
                 if (SVH_DIAG_AB == 0 && !FL) {
                     // lgkmcnt(5 or 6) alone (PATHS: and the two ring writes since the pairs' reads;
-                    // DM = 2: the pairs of two steps are four reads)
-                    __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0) + (DM == 2 ? 2 : 0)) << 8));
+                    // DM = 2: the pairs of two steps are four reads; QD: two again, one quad per step)
+                    __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0) + (DM == 2 && !QD ? 2 : 0)) << 8));
                     __builtin_amdgcn_sched_barrier(0);                         // ahead of both steps' uses
                 }
             }
@@ -567,7 +626,10 @@
         for (uint32_t j = 0; j < rem; ++j) {
             const float4 h = *reinterpret_cast<const float4*>(strm + (e0 + j) * kDE);
             const float roff = adr[e0 + j];
-            if constexpr (DM == 2) {
+            if constexpr (QD) {
+                const f4 e = lds_ld4(__builtin_bit_cast(uint32_t, roff) + lane * 16u);
+                step2(h, SX ? xsf[e0 + j] : 0.0f, (f2){e.x, e.y}, (f2){e.z, e.w});
+            } else if constexpr (DM == 2) {
                 const uint32_t a = __builtin_bit_cast(uint32_t, roff) + lane * 4u;
                 step2(h, SX ? xsf[e0 + j] : 0.0f, (f2){lds_ld1(a), lds_ld1(a + 256u)},
                       (f2){lds_ld1(a + kDRS2 * 4u), lds_ld1(a + kDRS2 * 4u + 256u)});
@@ -584,8 +646,23 @@
             // the slots of group k - 1, last read in block k - 1), the loads of group k + 5, the streams
             // of block k + 2 (into the buffer of block k - 1) and the symbols of block k + 3; its LDS
             // writes are complete (lgkmcnt(0)) when it arrives at the block's barrier
+            // Quad ring timing (QD): group k + 4 is issued during block k and has landed in LDS when this
+            // wave's vmcnt(0) below completes, ahead of barrier k (the one that ends block k).  Its first
+            // reader is a step wave's prefetch at the end of block k + 2 (block kb reads columns
+            // 64 kb + 1 .. 64 kb + 130: groups kb .. kb + 2), behind barriers k and k + 1, which that wave
+            // has passed: an LDS-DMA write is ordered for another wave's read by the issuer's vmcnt and a
+            // barrier, and here there are two.  The slots it lands in are those of group k - 1 (and, every
+            // fifth block, the mirror, last read in block k - 2), last read in block k - 1 by reads whose
+            // values the steps of that block used, so they had returned before barrier k - 1, which this
+            // wave passed before issuing.  (The wait could move behind barrier k, ahead of barrier k + 1,
+            // by the same argument; the loader wave has nothing to do in that time, so it stays here.)
             for (uint32_t k = 0; k < nbmax; ++k) {
-                if (!flr) {
+                if constexpr (QD) {
+                    sbuildl(k + 2);
+                    symloadl(k + 3);
+                    qfill(k + 4, 0, 1);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                } else if (!flr) {
                     sbuildl(k + 2);
                     symloadl(k + 3);
                     lwritel(k + 4);

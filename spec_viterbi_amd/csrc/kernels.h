@@ -226,6 +226,8 @@ struct PipeModel {
     uint32_t hx_exist;      // BandModel::hx_exist (heavy x: 0 = F, 1 = S)
     uint32_t hl_exist;      // BandModel::hl_exist
     uint32_t ties_heavy;    // every light position with an F term has it win ties
+    uint32_t dqd;           // diagonal plan (in the padding ahead of stamps), SVH_DIAG_QUAD at model creation:
+                            // 1 = never, 2 = wherever eligible the quad ring (dtab4), 0 = diag_quad_for's rule
     unsigned long long* stamps;  // diagnostics (SVH_PIPE_DEBUG): [ticket][W][8] counters, or null
     uint32_t diag;               // diagnostics with stamps (SVH_PIPE_DEBUG bits > 1): 1 = no boundary
                                  // exchange (every wave runs as block 0; timing only, wrong results)
@@ -239,6 +241,10 @@ struct PipeModel {
     const float* dtab2;
     uint32_t nrng2;
     uint32_t dsm;           // SVH_DIAG_SM at model creation: 1 or 2 forces that many diagonals per lane, 0 = diag_sm_for's rule
+    // diagonal plan, two diagonals per lane with the quad ring (diag.hip QD): the same values once more,
+    // [S][128 nrng2] float4 {ea[c], ea[(c + 64) % NP], eb[c], eb[(c + 64) % NP]} (NP = 128 nrng2): what a
+    // lane's two diagonals need of one step in 16 bytes; null: the plane layout only
+    const float4* dtab4;
 };
 constexpr int kPipeStamps = 15;  // written only by -DSVH_PIPE_DIAG builds of pipe.hip
 // Per-batch scratch of the pipelined kernel (sized for `rows` rows).
@@ -318,7 +324,7 @@ inline size_t pipe_path_lds_bytes(uint32_t W) { return (size_t)W * 8 * kPQuadStr
 // A workgroup is diag_waves_for(nseq) sequences x one range; rows whose speculation fails are re-run
 // in the same launch.  A scores row starts at observation 0 or resumes at begin > 0 from v_in.
 uint32_t diag_waves_for(uint64_t nseq);
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1, bool ld = false);
+size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1, bool ld = false, bool quad = false);
 // Diagonals per lane of a scores launch (1 or 2).  Two -- ranges of 128 diagonals, half as many waves,
 // each paying the step's per-wave part once for 128 positions -- where one per lane would put more
 // than one wave on a SIMD: ceil(nseq / W) W nrng > 4 CUs.  Rows resumed from v_in (the _spec tail,
@@ -330,6 +336,15 @@ uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths
 // workgroup on a CU (a step wave is then alone on its SIMD); PipeModel::dld (SVH_DIAG_LOADER = 0 / 1)
 // forces either for every scores launch whose LDS fits.
 bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
+// The quad ring of a two-diagonal loader-wave launch (diag.hip QD): every ring column holds the four
+// table values of a lane's two diagonals, so a step's table read is one 16-byte LDS read, and the
+// loader wave refills a symbol's group with one LDS-DMA instruction.  Where the launch runs two
+// diagonals per lane with the loader wave, the model has the table (dtab4: uploaded where
+// diag_quad_table_fits) and the wider ring fits the CU's LDS; PipeModel::dqd (SVH_DIAG_QUAD = 0 / 1)
+// forces it off, or on wherever eligible.  The floor launch (dld = 3) reads no ring and keeps the planes.
+bool diag_quad_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
+// Whether any quad launch of a model can fit (the narrowest workgroup's): what uploads dtab4.
+bool diag_quad_table_fits(uint32_t S, uint32_t P, bool sx);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
 hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
 // Model sets (diag.hip diag_set_kernel, runtime.cpp BatchSet): one launch over the workgroups of many

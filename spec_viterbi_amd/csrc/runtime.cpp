@@ -724,10 +724,26 @@ PipePlan make_pipe_plan(const HostModel& hm, uint32_t sm, uint32_t waves, bool w
                 pp.dtab2[((size_t)o * 2) * NP2 + p] = d[0];
                 pp.dtab2[((size_t)o * 2 + 1) * NP2 + p] = d[1];
             }
+        // the quad ring (diag.hip QD): the planes' values re-paired, entry c = what the two diagonals
+        // of a lane at column c read in one step, so that a step's table read is 16 bytes
+        pp.dtab4.resize((size_t)S * NP2 * 4);
+        for (uint32_t o = 0; o < S; ++o) {
+            const float* ea = pp.dtab2.data() + ((size_t)o * 2) * NP2;
+            const float* eb = ea + NP2;
+            float* d = pp.dtab4.data() + (size_t)o * NP2 * 4;
+            for (uint32_t c = 0; c < NP2; ++c) {
+                const uint32_t c2 = (c + 64) % NP2;
+                d[4 * c] = ea[c];
+                d[4 * c + 1] = ea[c2];
+                d[4 * c + 2] = eb[c];
+                d[4 * c + 3] = eb[c2];
+            }
+        }
         if (sh.bw[0] < kInfH) {  // cannot happen (analyze_band: p > 0), but the wrap depends on it
             pp.nrng = pp.nrng2 = 0;
             pp.dtab.clear();
             pp.dtab2.clear();
+            pp.dtab4.clear();
         }
     }
     // decoded paths: term flags per position (as BandPlan::pflags with heavy feeder F) and the
@@ -833,6 +849,11 @@ void DevicePipePlan::upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream
             d_dtab2.upload(p.dtab2.data(), p.dtab2.size() * 4, s);
             view.dtab2 = d_dtab2.as<float>();
             view.nrng2 = p.nrng2;
+            // the quad ring's table, for models of which some quad launch fits the LDS (diag_quad_for)
+            if (p.dtab4.size() == (size_t)S * p.P * 4 && diag_quad_table_fits(S, p.P, p.sx)) {
+                d_dtab4.upload(p.dtab4.data(), p.dtab4.size() * 4, s);
+                view.dtab4 = d_dtab4.as<float4>();
+            }
         }
         // SVH_DIAG_SM = 1 / 2: that many diagonals per lane for every scores launch (tests, A/B)
         if (const char* e = std::getenv("SVH_DIAG_SM")) {
@@ -841,6 +862,8 @@ void DevicePipePlan::upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream
         }
         // SVH_DIAG_LOADER = 0 / 1: without / with the loader wave for every scores launch (tests, A/B)
         if (const char* e = std::getenv("SVH_DIAG_LOADER"); e && *e) view.dld = std::atoi(e) ? 2u : 1u;
+        // SVH_DIAG_QUAD = 0 / 1: the plane layout / the quad ring wherever eligible (tests, A/B)
+        if (const char* e = std::getenv("SVH_DIAG_QUAD"); e && *e) view.dqd = std::atoi(e) ? 2u : 1u;
     }
     view.emax2 = p.emax2;
     // the pair-table step wherever it applies: TM = 4 (indexed operands, packed feeder terms:
@@ -1466,9 +1489,10 @@ void Model::spec_build(uint32_t level, hipStream_t s) {
 // What the pass over nseq rows at `level` would run (nseq 0: the model alone), as layers: the fused
 // plan's fields, under the chain plan's, under the pipelined or diagonal plan's, under the chunk
 // route's -- each layer only where the resolved plan has it.
-svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
+svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level, uint64_t* quad_lds) const {
     svh_model_info i;
     std::memset(&i, 0, sizeof(i));
+    if (quad_lds) *quad_lds = 0;
     // level >= 2 runs only the tail on step kernels, and no decoded paths: a path batch then reports
     // the scores plan of a view without scratch
     const bool steps = level <= 1 || spec_level < 2;
@@ -1537,6 +1561,9 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level) const {
         if (!pq) {  // scores on the diagonal plan
             i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
             i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm, diag_loader_for(pipe.view, nseq, false, false));
+            // (the plane layout's, also where the launch keeps the quad ring: svh_batch_diag_quad gives that)
+            if (quad_lds && diag_quad_for(pipe.view, nseq, false, false))
+                *quad_lds = diag_lds_bytes(w, host.S, pipe.plan.P, 2, true, true);
         } else {  // decoded paths on the diagonal plan
             i.diag_sm = 1;
             i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);

@@ -148,6 +148,8 @@ struct PipePlan {
     // ... two diagonals per lane: [S][2][128 nrng2] floats, ea plane then eb plane per symbol
     std::vector<float> dtab2;
     uint32_t nrng2 = 0;
+    // ... the quad ring's table: [S][128 nrng2] float4 {ea[c], ea[(c + 64) % NP], eb[c], eb[(c + 64) % NP]}
+    std::vector<float> dtab4;
     // _spec level 2 on this plan (pipe_l2.hip): the largest finite ea = fl(E_o[p] + aw_p), or +inf
     // when some score is negative (its margin check needs every score >= 0) or the plan is wide
     float emax2 = 0.0f;
@@ -162,7 +164,7 @@ PipePlan make_pipe_plan(const HostModel& hm, uint32_t sm = 0, uint32_t waves = 0
 
 struct DevicePipePlan {
     PipePlan plan;
-    DeviceBuffer d_tab, d_e0, d_start, d_lrow, d_hc, d_stamps, d_pflags, d_spos, d_dtab, d_dtab2;
+    DeviceBuffer d_tab, d_e0, d_start, d_lrow, d_hc, d_stamps, d_pflags, d_spos, d_dtab, d_dtab2, d_dtab4;
     PipeModel view{};
     void upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream_t s);
     void report_stamps(uint32_t nseq) const;  // diagnostic (SVH_PIPE_DEBUG): first sequence's waves
@@ -261,7 +263,8 @@ struct Model {
     const DevicePipePlan& pipe_plan(const PassPlan& p) const { return p.step == StepKernel::PipeWide ? pipe_wide : pipe; }
     const DevicePlan* fused_plan(bool paths) const;
     void spec_build(uint32_t level, hipStream_t s);
-    svh_model_info info(uint32_t nseq = 0, bool paths = false, uint32_t level = 0) const;
+    // quad_lds: the LDS of the batch's diagonal-plan launch where it keeps the quad ring (diag_quad_for), else 0
+    svh_model_info info(uint32_t nseq = 0, bool paths = false, uint32_t level = 0, uint64_t* quad_lds = nullptr) const;
     // one pass of the step kernel of `p` over a batch view
     void launch_steps(const FusedBatch& b, const PassPlan& p, hipStream_t s) const;
 };

@@ -330,6 +330,14 @@ int svh_batch_plan(svh_batch_t b, uint32_t level, svh_model_info* info) {
     });
 }
 
+int svh_batch_diag_quad(svh_batch_t b, uint32_t level, int32_t* quad, uint64_t* lds_bytes) {
+    return guarded([&] {
+        require(b && quad && lds_bytes, "null argument");
+        b->get()->model->info(b->get()->nseq, b->get()->paths, level, lds_bytes);
+        *quad = *lds_bytes ? 1 : 0;
+    });
+}
+
 int svh_batch_destroy(svh_batch_t b) {
     return guarded([&] {
         if (b && b->view) throw svh::Error(SVH_E_INVALID, "a set's member is destroyed with its set (svh_batchset_destroy)");

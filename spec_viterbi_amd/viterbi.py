@@ -211,7 +211,13 @@ class DeviceBatch:
         diagonal plan (threads = 64 x sequences per workgroup, slots = 1, spec_bytes = 0)."""
         i = _lib.svh_model_info()
         _lib.check(_lib.lib.svh_batch_plan(self._h, int(level), ctypes.byref(i)))
-        return {name: getattr(i, name) for name, _ in i._fields_}
+        plan = {name: getattr(i, name) for name, _ in i._fields_}
+        # the quad ring of the diagonal launch (svh_batch_diag_quad): lds_bytes above is the plane layout's
+        quad, lds = ctypes.c_int32(), ctypes.c_uint64()
+        _lib.check(_lib.lib.svh_batch_diag_quad(self._h, int(level), ctypes.byref(quad), ctypes.byref(lds)))
+        plan["diag_quad"] = int(quad.value)
+        plan["diag_quad_lds_bytes"] = int(lds.value)
+        return plan
 
     def fallbacks(self) -> int:
         """Rows of the last run that the pipelined kernel re-ran on the serial chain kernel
