@@ -20,13 +20,14 @@ HIP_SRCS  := $(wildcard $(CSRC)/fused_*.hip) $(CSRC)/misc.hip $(CSRC)/band.hip $
              $(CSRC)/pipe_tm1.hip $(CSRC)/pipe_tm1p.hip $(CSRC)/pipe_wide.hip $(CSRC)/pipe_wide_paths.hip $(CSRC)/pipe_paths.hip \
              $(CSRC)/spec2.hip $(CSRC)/pipe_l2.hip $(CSRC)/diag.hip $(CSRC)/diag_l2.hip
 HOST_SRCS := $(CSRC)/runtime.cpp $(CSRC)/svh_api.cpp $(CSRC)/HIP_impl.cpp $(CSRC)/data_reader.cpp $(CSRC)/stream.cpp \
-             $(CSRC)/seqreader.cpp $(CSRC)/chunker.cpp $(CSRC)/set_table.cpp $(CSRC)/batch_set.cpp $(CSRC)/dispatch.cpp
+             $(CSRC)/seqreader.cpp $(CSRC)/chunker.cpp $(CSRC)/set_table.cpp $(CSRC)/batch_set.cpp $(CSRC)/dispatch.cpp \
+             $(CSRC)/diag_launch.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(BUILD)/%.o,$(HOST_SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 
 CPP_TESTS := tests/cpp/test_HIP_impl tests/cpp/test_HIP_spec_impl tests/cpp/test_semantic_equality \
              tests/cpp/test_readers_asan tests/cpp/test_host_asan tests/cpp/test_diag_sizes_asan \
-             tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4
+             tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4 tests/cpp/test_diag_launch
 
 .PHONY: all lib oracle ref tests tools clean
 all: lib oracle tests tools ref
@@ -111,6 +112,11 @@ tests/cpp/test_set_table: tests/cpp/test_set_table.cpp $(CSRC)/set_table.cpp $(C
 tests/cpp/test_dispatch: tests/cpp/test_dispatch.cpp $(CSRC)/dispatch.cpp $(CSRC)/dispatch.h include/svh.h
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -Iinclude -I$(CSRC) \
 		-o $@ tests/cpp/test_dispatch.cpp $(CSRC)/dispatch.cpp
+
+# The diagonal plan's launch resolver (diag_launch.cpp: plain host code, no HIP) under the same sanitizers.
+tests/cpp/test_diag_launch: tests/cpp/test_diag_launch.cpp $(CSRC)/diag_launch.cpp $(CSRC)/diag_launch.h
+	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -I$(CSRC) \
+		-o $@ tests/cpp/test_diag_launch.cpp $(CSRC)/diag_launch.cpp
 
 # The reference benchmark harness's per-sequence call loop over HIP_impl / HIP_spec_impl.
 tools/bench_harness: tools/bench_harness.cpp $(LIB) include/HIP_impl.h include/HIP_spec_impl.h

@@ -32,7 +32,7 @@ BatchSet::BatchSet(Model* const* models, uint64_t nmodels, uint64_t nseq_, const
         sm[i].grouped = dp != nullptr;
         sm[i].nrng = dp ? dp->plan.nrng : 0;
         sm[i].nseq = nseq;
-        sm[i].waves = diag_waves_for(nseq);
+        sm[i].waves = dp ? diag_resolve(diag_caps(dp->view), {nseq}).W : 0;
     }
     std::string err;
     if (!build_set_table(sm.data(), sm.size(), &table, &err)) throw Error(SVH_E_UNSUPPORTED, "batch set: " + err);

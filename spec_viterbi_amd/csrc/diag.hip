@@ -83,8 +83,7 @@ static_assert(kPE + 2 <= kPS && kPS % 2 == 0 && kPE % 2 == 0 && kDK % kNS == 0 &
 static_assert(kPE == 2 && kDK % (2 * kAG) == 0,
               "address groups: read 2 kAG steps ahead into two register slots (group % 2), which repeat every block; "
               "a group's slot is free once the pairs of its last two steps are issued (kPE = 2)");
-constexpr uint32_t kDMaxSym = 32;
-static_assert(kDMaxSym == kDiagSetMaxSym, "kernels.h: what the runtime admits to a set launch");
+constexpr uint32_t kDMaxSym = kDiagMaxSym;
 // SVH_DIAG_AB (diagnostic builds, timing only, wrong results): 1 = no stream reads in the steps
 // (every step takes the block's first entry), 2 = no ring reads (the prologue's pairs), 3 = no
 // barrier between blocks, 4 = no prologue table loads, 5 = no partials / combine, 6 = return at entry,
@@ -163,21 +162,14 @@ __device__ __forceinline__ void exec_collect(uint64_t& alive) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__host__ __device__ constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx, uint32_t dm = 1, bool ld = false,
-                                                   bool quad = false) {
-    // ring [S][kDRS] float2 (dm = 2: [S][2][kDRS2] floats; quad: [S][kDRS] float4) | symbol template [S][8] |
-    // constants [W][2][kDK][kDE] | ring addresses [W][2][kDK] | X_SF [W][2][kDK] (sx only) | blocks [W] | rerun rows [W]
-    // (ld, the loader-wave variant: three stream buffers instead of two)
-    return ((size_t)S * (quad ? kDRS * 2 : dm == 2 ? kDRS2 : kDRS) * 2 + (size_t)S * 8 + (size_t)W * (ld ? 3 : 2) * kDK * (kDE + 1 + (sx ? 1 : 0)) + 2 * W) * 4;
-}
+// The LDS layouts are diag_launch.h's (host and device share them); the path variant's fold ring lies
+// behind this build's plain layout (diag_body.h).
+constexpr size_t diag_lds_main(uint32_t W, uint32_t S, bool sx) { return svh::diag_lds_main(kDK, W, S, sx, 1, false, false); }
 
 // Decoded paths (PATHS; the walk is pipe_paths.hip's diag entry): fold ring [W][kFS][64] floats behind
 // the scores variant's LDS, 16-byte aligned.
-constexpr uint32_t kFS = 8;  // steps between two folds of a wave's scores into mu partials
+constexpr uint32_t kFS = kDiagFoldSteps;  // steps between two folds of a wave's scores into mu partials
 static_assert(kDK % kFS == 0 && 32 % kFS == 0 && kFS * 8 == 64, "fold: lane l reduces 8 lanes of step l / 8");
-__host__ __device__ constexpr size_t diag_lds_paths(uint32_t W, uint32_t S, bool sx) {
-    return ((diag_lds_main(W, S, sx) + 15) & ~(size_t)15) + (size_t)W * kFS * 64 * 4;
-}
 
 // PATHS: the step also records what the path walk reads (kernels.h, "Diagonal plan, decoded paths"):
 // a decision bit per step, shifted into a word per lane (one compare, one add with carry), the
@@ -320,151 +312,92 @@ __global__ __launch_bounds__(256) void diag_finish_kernel(PipeModel m, FusedBatc
     if (*flag) pipe_rerun_row<2, 4, SX>(m, b, q, lds);
 }
 
-template <int W, int DM = 1>
-const void* diag_ptr(bool sx) {
-    return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, DM>)
-              : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM>);
+constexpr bool kVariants = SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0;  // (diagnostic builds keep the plain kernel)
+
+template <int W, bool SX, bool PATHS = false, int DM = 1, bool LD = false, bool FL = false, bool QD = false>
+const void* kernel_fn() {
+    return reinterpret_cast<const void*>(&diag_viterbi_kernel<W, SX, PATHS, DM, LD, FL, QD>);
 }
-template <int W, int DM>
-const void* diag_loader_ptr(bool sx) {
-    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) {  // (diagnostic builds keep the plain variant: diag_loader_for)
+// The instantiation of a resolved launch; null where there is none: the floor with workgroups of four
+// sequences only, the quad ring with blocks of 64 steps only, decoded paths without X_SF only (with
+// both PATHS and SX the block's body is past the compiler's limit for `#pragma unroll`, the 64 steps
+// are then unrolled in part, the register vectors indexed at run time, and the kernel is some 600
+// instructions per step: models whose S takes a term from F keep the chain path variant).
+template <int W, bool SX>
+const void* diag_kernel_w(const DiagLaunch& L, bool paths) {
+    if (paths) {
+        static_assert(kDK == 64, "the path records' block layout (two mask words, two checkpoints per block)");
+        if constexpr (!SX) return kernel_fn<W, false, true>();
         return nullptr;
-    } else {
-        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, DM, true>)
-                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, DM, true>);
     }
-}
-template <int W>
-const void* diag_quad_ptr(bool sx) {
-    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || kDK != 64) {
-        return nullptr;
-    } else {
-        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<W, true, false, 2, true, false, true>)
-                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, false, 2, true, false, true>);
-    }
-}
-// (Only the instantiations without X_SF: with both PATHS and SX the block's body is past the
-// compiler's limit for `#pragma unroll`, the 64 steps are then unrolled in part, the register
-// vectors indexed at run time, and the kernel is some 600 instructions per step.  Models whose S
-// takes a term from F keep the chain path variant: diag_paths_fit.)
-// (the floor: workgroups of four sequences only)
-template <int DM>
-const void* diag_floor_ptr(bool sx) {
-    if constexpr (SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) {
-        return nullptr;
-    } else {
-        return sx ? reinterpret_cast<const void*>(&diag_viterbi_kernel<4, true, false, DM, true, true>)
-                  : reinterpret_cast<const void*>(&diag_viterbi_kernel<4, false, false, DM, true, true>);
-    }
-}
-template <int W>
-const void* diag_paths_ptr() {
-    static_assert(kDK == 64, "the path records' block layout (two mask words, two checkpoints per block)");
-    return reinterpret_cast<const void*>(&diag_viterbi_kernel<W, false, true>);
-}
-
-}  // namespace
-
-uint32_t diag_waves_for(uint64_t nseq) { return nseq >= 4 ? 4u : nseq >= 2 ? 2u : 1u; }
-
-static size_t diag_lds(uint32_t W, uint32_t S, uint32_t P, bool sx, uint32_t dm = 1, bool ld = false, bool quad = false) {
-    const size_t rerun = (2 * (size_t)P + 2 * W) * 4;  // pipe_rerun_row: v[2][P], red[2][W]
-    const size_t mainb = diag_lds_main(W, S, sx, dm, ld, quad);
-    return mainb > rerun ? mainb : rerun;
-}
-
-// (the larger of the two kernels': models that use X_SF keep one stream more)
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm, bool ld, bool quad) {
-    return diag_lds(W, S, P, true, dm, ld, quad);
-}
-
-uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
-    if (paths || !m.dtab2 || !m.nrng2 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0) return 1;
-    if (m.dsm == 1 || m.dsm == 2) return m.dsm;
-    if (resumed || !m.cus) return 1;
-    const uint64_t W = diag_waves_for(nseq);
-    return (nseq + W - 1) / W * W * m.nrng > 4ull * m.cus ? 2 : 1;
-}
-
-bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
-    if (paths || !nseq || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || m.dld == 1) return false;  // (dld: kernels.h)
-    const uint32_t W = diag_waves_for(nseq);
-    const uint32_t dm = diag_sm_for(m, nseq, resumed, paths);
-    if (diag_lds(W, m.S, m.P, m.sx != 0, dm, true) > 160 * 1024) return false;
-    if (m.dld == 3) return W == 4;  // (the floor variant: svh_batch_step_floor_ms)
-    if (m.dld == 2) return true;
-    // a wave alone on its SIMD has no neighbour to hide the block's other work behind, and the third
-    // stream buffer costs no residency: launches of at most one workgroup per CU
-    return m.cus && (nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng) <= m.cus;
-}
-
-bool diag_quad_table_fits(uint32_t S, uint32_t P, bool sx) {
-    return SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0 && kDK == 64 && diag_lds(1, S, P, sx, 2, true, true) <= 160 * 1024;
-}
-
-bool diag_quad_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths) {
-    if (!m.dtab4 || m.dqd == 1 || m.dld == 3 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0 || kDK != 64) return false;
-    if (diag_sm_for(m, nseq, resumed, paths) != 2 || !diag_loader_for(m, nseq, resumed, paths)) return false;
-    return diag_lds(diag_waves_for(nseq), m.S, m.P, m.sx != 0, 2, true, true) <= 160 * 1024;
-}
-
-size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx) { return diag_lds_paths(W, S, sx); }
-
-// The path variant keeps two workgroups on a CU at every width (the headline's 494 workgroups need
-// them on 256 CUs): a model whose LDS does not allow that is not planned on it; nor is one whose S
-// takes a term from F (sx: no such instantiation, see diag_paths_ptr).
-bool diag_paths_fit(uint32_t S, bool sx) {
-    return !sx && SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0 && kDK == 64 && S > 0 && S <= kDMaxSym &&
-           diag_lds_paths(4, S, sx) <= kDiagPathsLdsMax;
-}
-
-hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream) {
-    const bool paths = b.cmask != nullptr;
-    if (!m.dtab || m.nrng == 0 || m.SM != 2 || m.S == 0 || m.S > kDMaxSym || (size_t)m.nrng * 64 > m.P || m.wide ||
-        b.run_mask || (b.v_in && !b.v_in_row) || !x.part || !x.done || !x.viol || b.nseq > x.rows || x.G < m.nrng)
-        return hipErrorInvalidValue;
-    // decoded paths: every record buffer, every row from observation 0, F winning every tie (one
-    // compare per decision bit), two workgroups per CU
-    if (paths && (!b.cmask_off || !b.ckpt || !b.ckpt_off || !b.fck || !b.fck_off || !b.hrec || !b.hrec_off || !b.prec ||
-                  !b.prec_off || b.v_in || !m.ties_heavy || !diag_paths_fit(m.S, m.sx != 0)))
-        return hipErrorInvalidValue;
-    if (b.nseq == 0) return hipSuccess;
-    const uint32_t W = diag_waves_for(b.nseq);
-    const uint32_t dm = diag_sm_for(m, b.nseq, b.v_in != nullptr, paths);
-    if (dm == 2 && ((size_t)m.nrng2 * 128 != m.P || x.G < m.nrng2)) return hipErrorInvalidValue;
-    const bool sx = m.sx != 0;
-    const bool ld = diag_loader_for(m, b.nseq, b.v_in != nullptr, paths);
-    const bool quad = diag_quad_for(m, b.nseq, b.v_in != nullptr, paths);
-    const void* fn = paths     ? (W == 4 ? diag_paths_ptr<4>() : W == 2 ? diag_paths_ptr<2>() : diag_paths_ptr<1>())
-                     : ld && m.dld == 3 ? (dm == 2 ? diag_floor_ptr<2>(sx) : diag_floor_ptr<1>(sx))
-                     : quad    ? (W == 4 ? diag_quad_ptr<4>(sx) : W == 2 ? diag_quad_ptr<2>(sx) : diag_quad_ptr<1>(sx))
-                     : ld      ? (dm == 2 ? (W == 4 ? diag_loader_ptr<4, 2>(sx) : W == 2 ? diag_loader_ptr<2, 2>(sx) : diag_loader_ptr<1, 2>(sx))
-                                          : (W == 4 ? diag_loader_ptr<4, 1>(sx) : W == 2 ? diag_loader_ptr<2, 1>(sx) : diag_loader_ptr<1, 1>(sx)))
-                     : dm == 2 ? (W == 4 ? diag_ptr<4, 2>(sx) : W == 2 ? diag_ptr<2, 2>(sx) : diag_ptr<1, 2>(sx))
-                               : (W == 4 ? diag_ptr<4>(sx) : W == 2 ? diag_ptr<2>(sx) : diag_ptr<1>(sx));
-    size_t lds = paths ? diag_lds_paths(W, m.S, sx) : diag_lds(W, m.S, m.P, sx, dm, ld, quad);
-    if (lds > 160 * 1024 || !fn) return hipErrorInvalidValue;
-    const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * (dm == 2 ? m.nrng2 : m.nrng);
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    // even placement: a launch that fits the chip gets its LDS request raised so that no CU can take
-    // more than ceil(grid / CUs) of its workgroups (the dispatcher would otherwise stack up to four
-    // on some CUs and leave others empty; the kernel ends with its most loaded CU)
-    if (m.cus) {
-        const uint64_t per_cu = (grid + m.cus - 1) / m.cus;
-        if (per_cu * lds <= 160 * 1024) {
-            const size_t cap = (160 * 1024 / per_cu) & ~(size_t)511;
-            lds = cap > lds ? cap : lds;
+    if constexpr (kVariants) {
+        if (L.floor) {
+            if constexpr (W == 4) return L.dm == 2 ? kernel_fn<4, SX, false, 2, true, true>() : kernel_fn<4, SX, false, 1, true, true>();
+            return nullptr;
         }
+        if constexpr (kDK == 64)
+            if (L.quad) return kernel_fn<W, SX, false, 2, true, false, true>();
+        if (L.loader) return L.dm == 2 ? kernel_fn<W, SX, false, 2, true>() : kernel_fn<W, SX, false, 1, true>();
     }
+    if (L.loader || L.quad || L.floor) return nullptr;
+    return L.dm == 2 ? kernel_fn<W, SX, false, 2>() : kernel_fn<W, SX>();
+}
+const void* diag_kernel(const DiagLaunch& L, bool paths, bool sx) {
+    switch (L.W) {
+        case 4: return sx ? diag_kernel_w<4, true>(L, paths) : diag_kernel_w<4, false>(L, paths);
+        case 2: return sx ? diag_kernel_w<2, true>(L, paths) : diag_kernel_w<2, false>(L, paths);
+        case 1: return sx ? diag_kernel_w<1, true>(L, paths) : diag_kernel_w<1, false>(L, paths);
+    }
+    return nullptr;
+}
+
+// A (model, batch, scratch) view the scores kernel (b.cmask null) or the paths kernel takes: the
+// model's shape (diag_launch.h), rows resumed with their own v_in, the scratch of this many rows and
+// ranges; decoded paths: every record buffer, every row from observation 0.
+bool diag_view_ok(const PipeModel& m, const FusedBatch& b, const PipeScratch& x) {
+    if (!m.dtab || !diag_model_ok(diag_caps(m)) || b.run_mask || (b.v_in && !b.v_in_row) || !x.part || !x.done || !x.viol ||
+        b.nseq > x.rows || x.G < m.nrng)
+        return false;
+    return !b.cmask || (b.cmask_off && b.ckpt && b.ckpt_off && b.fck && b.fck_off && b.hrec && b.hrec_off && b.prec && b.prec_off && !b.v_in);
+}
+
+hipError_t launch_fn(const void* fn, uint64_t grid, uint32_t threads, size_t lds, void** args, hipStream_t stream) {
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
+    return hipLaunchKernel(fn, dim3((uint32_t)grid), dim3(threads), args, lds, stream);
+}
+
+}  // namespace
+
+DiagCaps diag_caps(const PipeModel& m) {
+    DiagCaps c;
+    c.S = m.S, c.P = m.P, c.nrng = m.nrng, c.nrng2 = m.nrng2, c.SM = m.SM, c.cus = m.cus;
+    c.sx = m.sx != 0, c.wide = m.wide != 0, c.ties_heavy = m.ties_heavy != 0;
+    c.dtab2 = m.dtab2 != nullptr, c.dtab4 = m.dtab4 != nullptr;
+    c.dsm = m.dsm, c.dld = m.dld, c.dqd = m.dqd;
+    c.dk = kDK, c.variants = kVariants;
+    return c;
+}
+
+bool diag_layout_fits(uint32_t S, uint32_t P, uint32_t dm) { return diag_widest_fits(kDK, S, P, dm); }
+bool diag_quad_table_fits(uint32_t S, uint32_t P, bool sx) { return diag_quad_fits(kDK, kVariants, S, P, sx); }
+bool diag_paths_fit(uint32_t S, bool sx) { return svh::diag_paths_fit(kDK, kVariants, S, sx); }
+bool diag_set_model_ok(const PipeModel& m) { return m.dtab && !m.sx && diag_model_ok(diag_caps(m)); }
+
+hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream, bool step_floor) {
+    const bool paths = b.cmask != nullptr;
+    if (!diag_view_ok(m, b, x)) return hipErrorInvalidValue;
+    const DiagLaunch L = diag_resolve(diag_caps(m), {b.nseq, b.v_in != nullptr, paths, step_floor});
+    const void* fn = diag_kernel(L, paths, m.sx != 0);
+    if (!L.ok || !fn || x.G < L.ranges) return hipErrorInvalidValue;
+    if (b.nseq == 0) return hipSuccess;
     PipeModel mm = m;
     FusedBatch bb = b;
     PipeScratch xx = x;
     void* args[] = {&mm, &bb, &xx};
-    const hipError_t e = hipLaunchKernel(fn, dim3((uint32_t)grid), dim3(64 * (W + (ld ? 1 : 0))), args, lds, stream);
+    const hipError_t e = launch_fn(fn, L.grid, L.threads, L.lds_request, args, stream);
 #if SVH_DIAG_FINISH
     if (e != hipSuccess) return e;
     const void* fin = m.sx ? reinterpret_cast<const void*>(&diag_finish_kernel<true>)
@@ -476,26 +409,23 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
 }
 
 hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out) {
-    if (!host || !first_host || !out || ne == 0 || first_host[0] != 0 || SVH_DIAG_AB != 0 || SVH_DIAG_FINISH != 0)
-        return hipErrorInvalidValue;
+    if (!host || !first_host || !out || ne == 0 || first_host[0] != 0 || !kVariants) return hipErrorInvalidValue;
     const uint32_t nseq = host[0].b.nseq;
     if (nseq == 0) return hipErrorInvalidValue;
-    const uint32_t W = diag_waves_for(nseq);
+    const uint32_t W = diag_resolve(diag_caps(host[0].m), {nseq}).W;
     size_t lds = 0;
     for (uint32_t i = 0; i < ne; ++i) {
         const PipeModel& m = host[i].m;
         const FusedBatch& b = host[i].b;
-        const PipeScratch& x = host[i].x;
-        // launch_diag's conditions for a scores launch, and the set's own: no X_SF term, one W
-        if (!m.dtab || m.nrng == 0 || m.SM != 2 || m.S == 0 || m.S > kDMaxSym || (size_t)m.nrng * 64 > m.P || m.wide ||
-            m.sx || b.run_mask || b.cmask || (b.v_in && !b.v_in_row) || !x.part || !x.done || !x.viol || b.nseq != nseq ||
-            b.nseq > x.rows || x.G < m.nrng || !b.symbols || !b.sym_off || !b.begin || !b.end || !b.scores)
+        // a scores view launch_diag takes, and the set's own conditions: no X_SF term, one W, every input
+        if (!diag_view_ok(m, b, host[i].x) || !diag_set_model_ok(m) || b.cmask || b.nseq != nseq || !b.symbols || !b.sym_off ||
+            !b.begin || !b.end || !b.scores)
             return hipErrorInvalidValue;
         const uint64_t blocks = ((uint64_t)nseq + W - 1) / W * m.nrng;
         if (first_host[i + 1] < first_host[i] || (uint64_t)first_host[i + 1] - first_host[i] != blocks) return hipErrorInvalidValue;
-        lds = std::max(lds, diag_lds(W, m.S, m.P, false));
+        lds = std::max(lds, diag_lds_scores(kDK, W, m.S, m.P, false, 1, false, false));  // (the plain variant, one diagonal per lane)
     }
-    if (first_host[ne] > 0x7FFFFFFFu || lds > 160 * 1024) return hipErrorInvalidValue;
+    if (first_host[ne] > 0x7FFFFFFFu || lds > kDiagLdsMax) return hipErrorInvalidValue;
     out->grid = first_host[ne];
     out->lds_bytes = lds;
     out->waves = W;
@@ -511,24 +441,12 @@ hipError_t launch_diag_set(const DiagSetEntry* host, const uint32_t* first_host,
     const void* fn = L.waves == 4   ? reinterpret_cast<const void*>(&diag_set_kernel<4>)
                      : L.waves == 2 ? reinterpret_cast<const void*>(&diag_set_kernel<2>)
                                     : reinterpret_cast<const void*>(&diag_set_kernel<1>);
-    size_t lds = L.lds_bytes;
-    // even placement over the whole grid, as launch_diag's
-    if (cus) {
-        const uint64_t per_cu = (L.grid + cus - 1) / cus;
-        if (per_cu * lds <= 160 * 1024) {
-            const size_t cap = (160 * 1024 / per_cu) & ~(size_t)511;
-            lds = cap > lds ? cap : lds;
-        }
-    }
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     const DiagSetEntry* ea = entries;
     const uint32_t* fa = first;
     uint32_t na = ne;
     void* args[] = {&ea, &fa, &na};
-    return hipLaunchKernel(fn, dim3((uint32_t)L.grid), dim3(64 * L.waves), args, lds, stream);
+    // even placement over the whole grid
+    return launch_fn(fn, L.grid, 64 * L.waves, even_placement_lds(L.grid, cus, L.lds_bytes), args, stream);
 }
 
 }  // namespace svh

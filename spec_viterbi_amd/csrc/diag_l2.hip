@@ -66,7 +66,7 @@ constexpr uint32_t kDRS = kDR + 64;   // slots per symbol plane
 constexpr uint32_t kDG = kDR / kDK;   // ring groups
 constexpr uint32_t kCP = kDK / 2;     // 16-byte chunks of a plane's group (two columns each)
 constexpr uint32_t kLB = kDK / 2;     // chunks per block: a block consumes one group of columns
-constexpr uint32_t kDMaxSym = 32;
+constexpr uint32_t kDMaxSym = kDiagMaxSym;
 
 #ifndef SVH_DL2_PS
 #define SVH_DL2_PS 3
@@ -404,7 +404,7 @@ size_t diag_l2_lds_bytes(uint32_t W, uint32_t S) { return diag_l2_lds(W, S); }
 
 bool diag_l2_supported(const PipeModel& m) {
     return m.dtab && m.nrng && !m.wide && !m.sx && m.S > 0 && m.S <= kDMaxSym && (size_t)m.nrng * 64 <= m.P &&
-           m.emax2 < kInf && 2 * diag_l2_lds(4, m.S) <= 160 * 1024;
+           m.emax2 < kInf && 2 * diag_l2_lds(kDiagMaxWaves, m.S) <= kDiagLdsMax;
 }
 
 hipError_t launch_diag_l2(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream) {
@@ -414,18 +414,9 @@ hipError_t launch_diag_l2(const PipeModel& m, const FusedBatch& b, const PipeScr
     if (b.nseq == 0) return hipSuccess;
     const uint32_t W = diag_waves_for(b.nseq);
     const void* fn = W == 4 ? diag_l2_ptr<4>() : W == 2 ? diag_l2_ptr<2>() : diag_l2_ptr<1>();
-    size_t lds = diag_l2_lds(W, m.S);
     const uint64_t grid = ((uint64_t)b.nseq + W - 1) / W * m.nrng;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    // even placement, as launch_diag: a launch that fits the chip gets its LDS request raised so
-    // that no CU can take more than ceil(grid / CUs) of its workgroups
-    if (m.cus) {
-        const uint64_t per_cu = (grid + m.cus - 1) / m.cus;
-        if (per_cu * lds <= 160 * 1024) {
-            const size_t cap = (160 * 1024 / per_cu) & ~(size_t)511;
-            lds = cap > lds ? cap : lds;
-        }
-    }
+    const size_t lds = even_placement_lds(grid, m.cus, diag_l2_lds(W, m.S));
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -1,8 +1,8 @@
 // Which kernels run a pass (DESIGN.md "Dispatch"): plain host code, no HIP.  Model::Model fills a
 // ModelCaps once; every consumer -- Batch::load / run, Model::launch_steps, Model::info, the
 // time-parallel pass, the step floor, the model sets -- asks resolve_pass and decides nothing itself.
-// The resolver chooses a plan, not a grid: waves, slots and LDS sizes of a launch stay with the
-// kernels (diag_waves_for, diag_sm_for, pipew_waves_for, ...).
+// The resolver chooses a plan, not a grid: the diagonal plan's launch is diag_resolve's (diag_launch.h);
+// waves, slots and LDS sizes of the pipelined and wide plans stay with their kernels (pipew_waves_for, ...).
 #pragma once
 
 #include <cstdint>

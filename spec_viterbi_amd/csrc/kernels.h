@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "diag_launch.h"
+
 namespace svh {
 
 constexpr int kMaxHeavy = 4;      // heavy rows a fused-kernel family can hold
@@ -227,20 +229,19 @@ struct PipeModel {
     uint32_t hl_exist;      // BandModel::hl_exist
     uint32_t ties_heavy;    // every light position with an F term has it win ties
     uint32_t dqd;           // diagonal plan (in the padding ahead of stamps), SVH_DIAG_QUAD at model creation:
-                            // 1 = never, 2 = wherever eligible the quad ring (dtab4), 0 = diag_quad_for's rule
+                            // 1 = never, 2 = wherever eligible the quad ring (dtab4), 0 = diag_resolve's rule
     unsigned long long* stamps;  // diagnostics (SVH_PIPE_DEBUG): [ticket][W][8] counters, or null
     uint32_t diag;               // diagnostics with stamps (SVH_PIPE_DEBUG bits > 1): 1 = no boundary
                                  // exchange (every wave runs as block 0; timing only, wrong results)
     uint32_t dld;                // diagonal plan (in the padding ahead of dtab2: the kernels' argument layout is
                                  // unchanged), SVH_DIAG_LOADER at model creation: 1 = never, 2 = always the
-                                 // loader-wave variant, 0 = diag_loader_for's rule; 3 (svh_batch_step_floor_ms's
-                                 // copy of the model only) = the plan's floor (diag.hip FL): timing only
+                                 // loader-wave variant, 0 = diag_resolve's rule
     // diagonal plan, two diagonals per lane (diag.hip DM = 2): the same table split into planes,
     // [S][2][128 nrng2] floats (ea plane, eb plane per symbol; 128 nrng2 = P), nrng2 ranges of 128
     // diagonals per sequence; null: one diagonal per lane only
     const float* dtab2;
     uint32_t nrng2;
-    uint32_t dsm;           // SVH_DIAG_SM at model creation: 1 or 2 forces that many diagonals per lane, 0 = diag_sm_for's rule
+    uint32_t dsm;           // SVH_DIAG_SM at model creation: 1 or 2 forces that many diagonals per lane, 0 = diag_resolve's rule
     // diagonal plan, two diagonals per lane with the quad ring (diag.hip QD): the same values once more,
     // [S][128 nrng2] float4 {ea[c], ea[(c + 64) % NP], eb[c], eb[(c + 64) % NP]} (NP = 128 nrng2): what a
     // lane's two diagonals need of one step in 16 bytes; null: the plane layout only
@@ -321,32 +322,24 @@ inline size_t pipe_path_lds_bytes(uint32_t W) { return (size_t)W * 8 * kPQuadStr
 // Diagonal plan (diag.hip): the latency plan's recurrence with every lane on an anti-diagonal of the
 // (position, observation) grid -- lane l of range r holds position (64 r + l + i) mod (64 nrng) after
 // step i, so a position's chain input is the lane's own previous score (no exchange between waves).
-// A workgroup is diag_waves_for(nseq) sequences x one range; rows whose speculation fails are re-run
-// in the same launch.  A scores row starts at observation 0 or resumes at begin > 0 from v_in.
-uint32_t diag_waves_for(uint64_t nseq);
-size_t diag_lds_bytes(uint32_t W, uint32_t S, uint32_t P, uint32_t dm = 1, bool ld = false, bool quad = false);
-// Diagonals per lane of a scores launch (1 or 2).  Two -- ranges of 128 diagonals, half as many waves,
-// each paying the step's per-wave part once for 128 positions -- where one per lane would put more
-// than one wave on a SIMD: ceil(nseq / W) W nrng > 4 CUs.  Rows resumed from v_in (the _spec tail,
-// time-parallel segments) and path batches keep one.  PipeModel::dsm (SVH_DIAG_SM) forces either for
-// every scores launch.
-uint32_t diag_sm_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
-// The loader-wave variant of a scores launch (diag.hip LD): the workgroup runs one wave more, which
-// does the blocks' ring refill and stream build for the step waves.  Where a launch puts at most one
-// workgroup on a CU (a step wave is then alone on its SIMD); PipeModel::dld (SVH_DIAG_LOADER = 0 / 1)
-// forces either for every scores launch whose LDS fits.
-bool diag_loader_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
-// The quad ring of a two-diagonal loader-wave launch (diag.hip QD): every ring column holds the four
-// table values of a lane's two diagonals, so a step's table read is one 16-byte LDS read, and the
-// loader wave refills a symbol's group with one LDS-DMA instruction.  Where the launch runs two
-// diagonals per lane with the loader wave, the model has the table (dtab4: uploaded where
-// diag_quad_table_fits) and the wider ring fits the CU's LDS; PipeModel::dqd (SVH_DIAG_QUAD = 0 / 1)
-// forces it off, or on wherever eligible.  The floor launch (dld = 3) reads no ring and keeps the planes.
-bool diag_quad_for(const PipeModel& m, uint64_t nseq, bool resumed, bool paths);
-// Whether any quad launch of a model can fit (the narrowest workgroup's): what uploads dtab4.
+// A workgroup is W sequences x one range; rows whose speculation fails are re-run in the same launch.
+// A scores row starts at observation 0 or resumes at begin > 0 from v_in.
+// Which variant a launch is -- two diagonals per lane (DM = 2), the loader wave (LD), the quad ring
+// (QD), the floor (FL) --, its grid, workgroup and LDS: diag_resolve (diag_launch.h), on the model's
+// and the build's DiagCaps.  diag.hip is the one translation unit that sees the build's macros.
+DiagCaps diag_caps(const PipeModel& m);
+// Upload-time questions of a table layout, in this build: does the widest plain launch with dm
+// diagonals per lane fit the LDS (dtab, dtab2); does any quad launch (dtab4).
+bool diag_layout_fits(uint32_t S, uint32_t P, uint32_t dm);
 bool diag_quad_table_fits(uint32_t S, uint32_t P, bool sx);
+// The model side of an entry a set launch takes (below): launch_diag's, and no X_SF term.
+bool diag_set_model_ok(const PipeModel& m);
 // b.cmask != nullptr selects the decoded-path variant (below; every sequence must start at step 0).
-hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream);
+// step_floor: the plan's floor -- the loader-wave launch with the loader wave idle, no LDS reads in
+// the steps, no partials, arrival count, combine or re-run (diag.hip FL) -- for
+// svh_batch_step_floor_ms (timing only; b's outputs must be scratch)
+hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratch& x, hipStream_t stream,
+                       bool step_floor = false);
 // Model sets (diag.hip diag_set_kernel, runtime.cpp BatchSet): one launch over the workgroups of many
 // (model, batch, scratch) triples.  A table of DiagSetEntry in device memory and a prefix table
 // first[ne + 1] of the entries' first blocks (set_table.h; first[ne] = the grid); a workgroup finds the
@@ -355,7 +348,6 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
 // diagonal per lane, no loader wave; every entry's batch has the same number of sequences (one W per
 // launch).  host[] is the host copy of the table at entries (validated as launch_diag validates its
 // arguments; its largest LDS footprint is the launch's); cus: the device's CUs (even placement, 0: off).
-constexpr uint32_t kDiagSetMaxSym = 32;  // (diag.hip kDMaxSym: the ring's symbol planes)
 struct DiagSetEntry {
     PipeModel m;
     FusedBatch b;
@@ -374,7 +366,7 @@ hipError_t launch_diag_set(const DiagSetEntry* host, const uint32_t* first_host,
 // one launch -- a lane advances two positions per chunk, so its chain input is again its own score.
 // Row q starts from the first observation's state in b.v_in (row q) and ends in b.scores (row q;
 // rows of 0 chunks are copied through); rows whose speculation fails are flagged in x.viol (re-run
-// by spec2_kernel, runtime.cpp).  Workgroups of diag_waves_for(nseq) sequences x one range.  Models
+// by spec2_kernel, runtime.cpp).  Workgroups of diag_waves_for(nseq) sequences x one range (diag_launch.h).  Models
 // whose S takes a term from F (sx), with a negative score (emax2 = +inf), more than 32 symbols or an
 // LDS footprint that keeps two workgroups off a CU are not supported.
 bool diag_l2_supported(const PipeModel& m);
@@ -398,14 +390,12 @@ hipError_t launch_diag_l2(const PipeModel& m, const FusedBatch& b, const PipeScr
 //          bit the recurrence's own value: fl(A_S + .) is monotone, so min_p fl(A_S + v_p) =
 //          fl(A_S + min_p v_p)
 constexpr uint32_t kDiagCkptEvery = 32;
-constexpr size_t kDiagPathsLdsMax = 80 * 1024;  // two workgroups per CU
 inline uint64_t diag_mask_words(uint64_t len, uint32_t nrng) { return len > 1 ? (len - 1 + 31) / 32 * (uint64_t)nrng * 64 : 0; }
 inline uint64_t diag_ckpt_floats(uint64_t len, uint32_t nrng) {
     return len ? ((len - 1) / kDiagCkptEvery + 1) * (uint64_t)nrng * 64 : 0;
 }
 inline uint64_t diag_mu_floats(uint64_t len, uint32_t nrng) { return (uint64_t)nrng * len; }
 inline uint64_t diag_cck_floats(uint64_t len, uint32_t nrng) { return len ? ((len - 1) / 32 + 1) * (uint64_t)nrng : 0; }
-size_t diag_paths_lds_bytes(uint32_t W, uint32_t S, bool sx);
 bool diag_paths_fit(uint32_t S, bool sx);  // S takes no term from F, and the LDS allows two workgroups per CU
 hipError_t launch_diag_traceback(const PipeModel& m, const FusedBatch& b, const uint64_t* path_off, int32_t* paths,
                                  const uint32_t* skip, hipStream_t stream);

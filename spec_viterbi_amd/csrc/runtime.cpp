@@ -840,16 +840,15 @@ void DevicePipePlan::upload(const PipePlan& p, uint32_t n, uint32_t S, hipStream
     view.sx = p.sx ? 1u : 0u;
     view.wide = p.wide ? 1u : 0u;
     view.rerun = !p.wide && pipe_rerun_fits(p.P, p.W) ? 1u : 0u;
-    if (p.nrng && !p.dtab.empty() && diag_lds_bytes(diag_waves_for(4), S, p.P) <= 160 * 1024) {
+    if (p.nrng && !p.dtab.empty() && diag_layout_fits(S, p.P, 1)) {
         d_dtab.upload(p.dtab.data(), p.dtab.size() * 4, s);
         view.dtab = d_dtab.as<float2>();
         view.nrng = p.nrng;
-        if (p.nrng2 && !p.dtab2.empty() && (size_t)p.nrng2 * 128 == p.P &&
-            diag_lds_bytes(diag_waves_for(4), S, p.P, 2) <= 160 * 1024) {
+        if (p.nrng2 && !p.dtab2.empty() && (size_t)p.nrng2 * 128 == p.P && diag_layout_fits(S, p.P, 2)) {
             d_dtab2.upload(p.dtab2.data(), p.dtab2.size() * 4, s);
             view.dtab2 = d_dtab2.as<float>();
             view.nrng2 = p.nrng2;
-            // the quad ring's table, for models of which some quad launch fits the LDS (diag_quad_for)
+            // the quad ring's table, for models of which some quad launch fits the LDS
             if (p.dtab4.size() == (size_t)S * p.P * 4 && diag_quad_table_fits(S, p.P, p.sx)) {
                 d_dtab4.upload(p.dtab4.data(), p.dtab4.size() * 4, s);
                 view.dtab4 = d_dtab4.as<float4>();
@@ -1145,8 +1144,7 @@ Model::Model(const HostModel& h, const svh_model_opts* opts) : host(h) {
                 // beyond that the latency plan's two-per-CU regime is faster (2405.chmm: 52 sequences;
                 // at 64 the diagonal plan takes 0.296 ms against 0.303, at 90 0.363 against 0.313,
                 // profiles/r06_diag/widths.log)
-                const uint32_t w = diag_waves_for(4);
-                caps.diag_max_nseq = std::min<uint32_t>(caps.pipe_max_nseq, w * (2 * cu_count / pipe.plan.nrng));
+                caps.diag_max_nseq = std::min<uint32_t>(caps.pipe_max_nseq, kDiagMaxWaves * (2 * cu_count / pipe.plan.nrng));
                 if (const char* e = std::getenv("SVH_DIAG_MAX_NSEQ")) caps.diag_max_nseq = (uint32_t)std::atoi(e);
             }
         }
@@ -1555,21 +1553,19 @@ svh_model_info Model::info(uint32_t nseq, bool paths, uint32_t level, uint64_t* 
     i.pipew_min_nseq = t.pipew_min_nseq;
     i.diag_max_nseq = t.diag_max_nseq;
     if (pl.step == StepKernel::Diag && level <= 1) {
-        const uint32_t w = diag_waves_for(nseq);
-        i.threads = (int32_t)(64 * w);
+        // what launch_diag launches (diag_launch.h), reported as svh_model_info always has: threads
+        // without the loader wave; lds_bytes of a scores launch with the X_SF stream whatever the model
+        // (the larger of the two kernels') and in the plane layout also where the launch keeps the
+        // quad ring, whose size only svh_batch_diag_quad gives
+        const DiagCaps dc = diag_caps(pipe.view);
+        const DiagLaunch L = diag_resolve(dc, {nseq, false, pq, false});
+        i.threads = (int32_t)(64 * L.W);
         i.slots = 1;
-        if (!pq) {  // scores on the diagonal plan
-            i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, false, false);
-            i.lds_bytes = diag_lds_bytes(w, host.S, pipe.plan.P, (uint32_t)i.diag_sm, diag_loader_for(pipe.view, nseq, false, false));
-            // (the plane layout's, also where the launch keeps the quad ring: svh_batch_diag_quad gives that)
-            if (quad_lds && diag_quad_for(pipe.view, nseq, false, false))
-                *quad_lds = diag_lds_bytes(w, host.S, pipe.plan.P, 2, true, true);
-        } else {  // decoded paths on the diagonal plan
-            i.diag_sm = 1;
-            i.lds_bytes = diag_paths_lds_bytes(w, host.S, pipe.plan.sx);
-        }
-    } else if (pl.step == StepKernel::Diag && !pq) {  // the _spec tail's launch
-        i.diag_sm = (int32_t)diag_sm_for(pipe.view, nseq, true, false);
+        i.diag_sm = (int32_t)L.dm;
+        i.lds_bytes = pq ? L.lds_bytes : diag_lds_scores(dc.dk, L.W, dc.S, dc.P, true, L.dm, L.loader, false);
+        if (quad_lds && L.quad) *quad_lds = diag_lds_scores(dc.dk, L.W, dc.S, dc.P, true, 2, true, true);
+    } else if (pl.step == StepKernel::Diag && !pq) {  // the _spec tail's launch: its rows resume
+        i.diag_sm = (int32_t)diag_resolve(diag_caps(pipe.view), {nseq, true, false, false}).dm;
     }
     if (nseq && pl.chunks == ChunkRoute::Spec2Pipe) {  // the chunks on the pipelined plan
         i.kernel = SVH_KERNEL_SPEC2_PIPE;
@@ -1872,10 +1868,7 @@ FusedBatch Batch::scores_view() const {
 const DevicePipePlan* Batch::set_plan() const {
     if (paths || plan.step != StepKernel::Diag) return nullptr;
     const DevicePipePlan* dp = &model->pipe_plan(plan);
-    const PipeModel& v = dp->view;
-    // (the rest: launch_diag's own conditions, which every diagonal table built so far meets)
-    if (v.sx || v.S == 0 || v.S > kDiagSetMaxSym || v.SM != 2 || v.wide || v.nrng == 0 || (size_t)v.nrng * 64 > v.P) return nullptr;
-    return dp;
+    return diag_set_model_ok(dp->view) ? dp : nullptr;
 }
 
 void Batch::begin_set_run(hipStream_t s, DiagSetEntry* e) {
@@ -2504,16 +2497,12 @@ float Batch::step_floor_ms(hipStream_t s, uint32_t reps) {
     if (!s) s = model->stream;
     // a batch whose scores pass runs the diagonal plan: that plan's floor -- its loader-wave launch
     // with the loader wave idle, no LDS reads in the steps and no partials, arrival count, combine or
-    // re-run (diag.hip FL, dld = 3), i.e. the prologue and the steps' arithmetic alone; every other
+    // re-run (diag.hip FL), i.e. the prologue and the steps' arithmetic alone; every other
     // batch: the latency plan's, if the scores pass of this many rows runs it
     const PassPlan sp = model->resolve(nseq, false, 0, true);
     const DevicePipePlan* dp = !paths && sp.step == StepKernel::Diag ? &model->pipe : nullptr;
-    PipeModel dview{};
-    if (dp) {
-        dview = dp->view;
-        dview.dld = 3;
-        if (!diag_loader_for(dview, nseq, false, false)) dp = nullptr;
-    }
+    // (no floor launch of fewer than four sequences, or where its LDS does not fit)
+    if (dp && !diag_resolve(diag_caps(dp->view), {nseq, false, false, true}).ok) dp = nullptr;
     const DevicePipePlan* pp = sp.no_diag == StepKernel::Pipe ? &model->pipe : nullptr;
     if (!dp && (!pp || pp->view.tm != 4 || pp->plan.W != 4))
         throw Error(SVH_E_UNSUPPORTED, "step floor: the batch's plan is neither the diagonal plan nor the pipelined latency plan (TM 4)");
@@ -2529,7 +2518,7 @@ float Batch::step_floor_ms(hipStream_t s, uint32_t reps) {
     hip_check(hipEventCreate(&e1), "hipEventCreate");
     float ms = 0;
     auto launch_floor = [&]() {
-        return dp ? launch_diag(dview, fb, floor_scratch.view, s) : launch_pipe(pp->view, fb, floor_scratch.view, s, true);
+        return dp ? launch_diag(dp->view, fb, floor_scratch.view, s, true) : launch_pipe(pp->view, fb, floor_scratch.view, s, true);
     };
     try {
         floor_scratch.note_launch(s);

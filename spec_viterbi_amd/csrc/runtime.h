@@ -263,7 +263,7 @@ struct Model {
     const DevicePipePlan& pipe_plan(const PassPlan& p) const { return p.step == StepKernel::PipeWide ? pipe_wide : pipe; }
     const DevicePlan* fused_plan(bool paths) const;
     void spec_build(uint32_t level, hipStream_t s);
-    // quad_lds: the LDS of the batch's diagonal-plan launch where it keeps the quad ring (diag_quad_for), else 0
+    // quad_lds: the LDS of the batch's diagonal-plan launch where it keeps the quad ring (DiagLaunch::quad), else 0
     svh_model_info info(uint32_t nseq = 0, bool paths = false, uint32_t level = 0, uint64_t* quad_lds = nullptr) const;
     // one pass of the step kernel of `p` over a batch view
     void launch_steps(const FusedBatch& b, const PassPlan& p, hipStream_t s) const;
@@ -368,7 +368,7 @@ struct Batch {
     // and read() go by -- without the launch; *e = the (model, batch, scratch) triple of that launch
     void begin_set_run(hipStream_t s, DiagSetEntry* e);
     // the diagonal plan of this batch's scores pass if a set launch can take it (nullptr: the
-    // member runs on its own): no X_SF term, at most kDiagSetMaxSym symbols
+    // member runs on its own): no X_SF term, at most kDiagMaxSym symbols
     const DevicePipePlan* set_plan() const;
 
   private:
@@ -381,7 +381,7 @@ struct Batch {
 // each with its own symbols copy, result arena, fault word and scratch, so everything that works on a
 // batch (read, pipe_fallbacks, the plan, the fault report) works on a member unchanged.  run()
 // launches every grouped member -- one whose own scores plan is the diagonal plan, without an X_SF
-// term, of at most kDiagSetMaxSym symbols -- in ONE launch of diag_set_kernel, then every other
+// term, of at most kDiagMaxSym symbols -- in ONE launch of diag_set_kernel, then every other
 // member's own Batch::run on the same stream.  Levels 0 and 1, scores only.
 struct BatchSet {
     std::mutex mu;  // run() / info() / elapsed_ms() of one set are serialised
