@@ -121,6 +121,15 @@ constexpr uint32_t kDMaxSym = kDiagMaxSym;
 #ifndef SVH_DIAG_QDMA
 #define SVH_DIAG_QDMA 1
 #endif
+// SVH_DIAG_RDPLACE (A/B of the quad-ring kernels' two-step body, diag_body.h block()): 0 = the order
+// of every other instantiation, the body's reads at its top with the quads' address adds among them
+// (in the bodies that read an address group), constants six steps ahead, quads two; 1 (the default,
+// -4 %: DESIGN.md 5l, "Read placement") = both address adds ahead of the reads in every body, so that
+// the two constants, the two quads and the group read issue in one run, and the constants two steps
+// ahead like the quads
+#ifndef SVH_DIAG_RDPLACE
+#define SVH_DIAG_RDPLACE 1
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif

@@ -361,7 +361,12 @@
 
     // software pipeline: stream entries of steps j .. j + kPS + 1 and ring pairs of j .. j + kPE + 1
     // in registers (slot j % kNS, j % kNE)
-    typedef float hvec __attribute__((ext_vector_type(4 * kNS)));
+    // (RP, SVH_DIAG_RDPLACE: the quad ring's read placement, block() below; with it the constants are
+    // read two steps ahead like the quads, PS / NS in the place of kPS / kNS)
+    constexpr int RP = (QD && SVH_DIAG_AB == 0) ? SVH_DIAG_RDPLACE : 0;
+    constexpr uint32_t PS = RP ? kPE : kPS, NS = PS + 2;
+    static_assert((RP == 0 || RP == 1) && kDK % NS == 0, "read placement; the register slots of step j repeat every block");
+    typedef float hvec __attribute__((ext_vector_type(4 * NS)));
     typedef float avec __attribute__((ext_vector_type(2 * kAG)));
     typedef float evec __attribute__((ext_vector_type(2 * DM * kNE)));
     hvec hq;
@@ -415,7 +420,7 @@
         eq[2 * (j % kNE) + 1] = e.y;
     };
 #pragma unroll
-    for (uint32_t j = 0; j < kPS; ++j) sread(0, j, j);
+    for (uint32_t j = 0; j < PS; ++j) sread(0, j, j);
     gread(aq, adr, 0, 0);
     gread(aq, adr, 0, kAG);
     if (SX) gread(xq, xsf, 0, 0);
@@ -549,7 +554,7 @@
         __builtin_amdgcn_sched_barrier(0);  // the block's work stays above the first check
 #pragma unroll
         for (uint32_t j = 0; j < kDK; ++j) {
-            const uint32_t a = (SVH_DIAG_AB == 1 || FL) ? 0u : j % kNS, b2 = FL ? 0u : j % kNE;
+            const uint32_t a = (SVH_DIAG_AB == 1 || FL) ? 0u : j % NS, b2 = FL ? 0u : j % kNE;
             const float4 h = make_float4(hq[4 * a], hq[4 * a + 1], hq[4 * a + 2], hq[4 * a + 3]);
             const float xs = SX ? xq[(SVH_DIAG_AB == 1 || FL) ? 0u : j % (2 * kAG)] : 0.0f;
             const f2 e = DM == 2 ? (f2){eq[4 * b2], eq[4 * b2 + 1]} : (f2){eq[2 * b2], eq[2 * b2 + 1]};
@@ -562,7 +567,7 @@
             // (four here and one group read, this step's or the one two steps back).  The compiler
             // places its own counted waits where this one does not suffice: the count is a matter
             // of speed only.
-            if (j % 2 == 0) {
+            if (RP == 0 && j % 2 == 0) {
                 if (SVH_DIAG_AB != 1 && !FL) {
                     sread(kb, j + kPS, (j + kPS) % kNS);
                     sread(kb, j + kPS + 1, (j + kPS + 1) % kNS);
@@ -580,6 +585,44 @@
                     // DM = 2: the pairs of two steps are four reads; QD: two again, one quad per step)
                     __builtin_amdgcn_s_waitcnt(0xC07F | (((SX ? 6 : 5) + (PATHS ? 2 : 0) + (DM == 2 && !QD ? 2 : 0)) << 8));
                     __builtin_amdgcn_sched_barrier(0);                         // ahead of both steps' uses
+                }
+            }
+            // The quad ring's read placement (RP = 1): the same reads as above with the quads' two
+            // address adds ahead of them in every body (the order above leaves one between the reads
+            // in the bodies that read an address group), so that the two constants, the two quads
+            // and the group read(s) issue in one run, and with the constants two steps ahead like the
+            // quads; everything fenced where it stands.  The wait's count: a body consumes the reads
+            // of the body before, LDS reads return in order, and behind that body's last read stand
+            // this body's four and, every other body, its group read (two with SX): lgkmcnt(4) or
+            // lgkmcnt(5 or 6).  The quads' distance is kPE as above: ring timing as it was.
+            if constexpr (RP == 1) {
+                if (j % 2 == 0) {
+                    uint32_t qa[2];
+#pragma unroll
+                    for (uint32_t i = 0; i < 2; ++i) {
+                        const float roff = aq[(j + kPE + i) % (2 * kAG)];
+                        qa[i] = __builtin_bit_cast(uint32_t, roff) + lane * 16u;
+                        asm volatile("" : "+v"(qa[i]));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    sread(kb, j + PS, (j + PS) % NS);
+                    sread(kb, j + PS + 1, (j + PS + 1) % NS);
+#pragma unroll
+                    for (uint32_t i = 0; i < 2; ++i) {
+                        const f4 e4 = lds_ld4(qa[i]);
+                        eq[4 * ((j + kPE + i) % kNE)] = e4.x;
+                        eq[4 * ((j + kPE + i) % kNE) + 1] = e4.y;
+                        eq[4 * ((j + kPE + i) % kNE) + 2] = e4.z;
+                        eq[4 * ((j + kPE + i) % kNE) + 3] = e4.w;
+                    }
+                    if (j % kAG == 0) {
+                        gread(aq, adr, kb, j + 2 * kAG);
+                        if (SX) gread(xq, xsf, kb, j + kAG);
+                        __builtin_amdgcn_s_waitcnt(0xC07F | ((SX ? 6 : 5) << 8));
+                    } else {
+                        __builtin_amdgcn_s_waitcnt(0xC07F | (4 << 8));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);  // ahead of both steps' uses
                 }
             }
             if constexpr (DM == 2) step2(h, xs, e, (f2){eq[4 * b2 + 2], eq[4 * b2 + 3]});
