@@ -130,6 +130,14 @@ constexpr uint32_t kDMaxSym = kDiagMaxSym;
 #ifndef SVH_DIAG_RDPLACE
 #define SVH_DIAG_RDPLACE 1
 #endif
+// SVH_DIAG_S2PAIR (A/B of the two-diagonal step's {F, c} pair, diag_body.h step2): 0 = the pair's
+// packed add and the sink's minimum as plain C++; the compiler then puts the minimum into another
+// register and moves F' beside it, one v_mov_b32 per step; 1 (the default, -2 %: DESIGN.md 5l, "The
+// two-diagonal step without its move") = both in one asm statement that advances the pair in place in a
+// fixed register pair (v[94:95]), no move
+#ifndef SVH_DIAG_S2PAIR
+#define SVH_DIAG_S2PAIR 1
+#endif
 #ifndef SVH_DIAG_DONE_STRIDE  // words between rows' arrival counts (the scratch holds 32 per row)
 #define SVH_DIAG_DONE_STRIDE 1
 #endif

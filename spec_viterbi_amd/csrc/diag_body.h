@@ -453,18 +453,35 @@
     auto step2 = [&](const float4& h, float xs, const f2& ea, const f2& eb) {
         XP.x = fminf(X2.x, X2.y);             // m: what the check and the sink need of the two scores
         const f2 Y = XP.xx + (f2){h.x, h.y};  // {A_F + m, A_S + m}
+#if SVH_DIAG_S2PAIR
+        // The pair advances in place, in one fixed register pair: the packed add {X_FF + F, X_SS + c}
+        // writes it, and the sink's minimum writes its second register.  Left to the compiler, the
+        // minimum goes to another register and a v_mov_b32 per step puts F' beside it.
+        // The same instructions on the same operands otherwise.  (The pair is read and written, and
+        // marked early-clobber: no other operand of the statement may share its registers.)
+        const f2 za = ea + FC.xx;             // {ea_a + F, ea_b + F}
+        const f2 zb = eb + X2;                // {eb_a + x_a, eb_b + x_b}
+        const f2 hzw = (f2){h.z, h.w};
+        if (SX) {
+            const float xf = xs + FC.x;       // X_SF + F
+            asm("v_pk_add_f32 %0, %0, %1\n\tv_min3_f32 v95, v95, %2, %3" : "+&{v[94:95]}"(FC) : "v"(hzw), "v"(Y.y), "v"(xf));
+        } else {
+            asm("v_pk_add_f32 %0, %0, %1\n\tv_min_f32 v95, v95, %2" : "+&{v[94:95]}"(FC) : "v"(hzw), "v"(Y.y));
+        }
+        if (SVH_DIAG_CMPX2) check_off(Y.x, FC.x);
+        else nviol += Y.x < FC.x ? 1u : 0u;
+        X2 = (f2){fminf(zb.x, za.x), fminf(zb.y, za.y)};
+#else
         const f2 Wv = FC + (f2){h.z, h.w};    // {F' = X_FF + F, X_SS + c}
         const f2 za = ea + FC.xx;             // {ea_a + F, ea_b + F}
         const f2 zb = eb + X2;                // {eb_a + x_a, eb_b + x_b}
-        // (the compiler puts this minimum into Y's pair and moves F' beside it, one v_mov per step
-        // that the one-diagonal step does not have; tying the minimum to Wv's second register with an
-        // asm statement made it two moves and 2.5 % slower)
         float cn = fminf(Wv.y, Y.y);
         if (SX) cn = fminf(cn, xs + FC.x);    // X_SF + F
         if (SVH_DIAG_CMPX2) check_off(Y.x, Wv.x);
         else nviol += Y.x < Wv.x ? 1u : 0u;
         X2 = (f2){fminf(zb.x, za.x), fminf(zb.y, za.y)};
         FC = (f2){Wv.x, cn};
+#endif
     };
     // PATHS, after an exec_collect: the last n <= kFS steps' scores (observations t0 .. t0 + n - 1) ->
     // the range's light minima.  Lane l takes lanes 8 (l % 8) .. + 7 of step l / 8; three DPP stages

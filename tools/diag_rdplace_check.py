@@ -19,6 +19,10 @@ keeps (diag_body.h block(), SVH_DIAG_RDPLACE = 1) shows in it as follows; the pa
   * No read stands behind the last wait.
 Prints the figures and exits 1 if one of them is off.  It reads only ds_read, s_waitcnt, s_barrier,
 v_pk_add_f32 and labels.
+
+step2_figures() counts what the two-diagonal step whose {F, c} pair advances in place (diag_body.h step2,
+SVH_DIAG_S2PAIR = 1) shows in the same block: 64 x 4 v_pk_add_f32, no v_add_f32 and no v_mov_b32 in a
+step (--step2 prints them; the build that leaves the pair to the compiler, = 0, has a move per step).
 """
 import argparse
 import re
@@ -40,6 +44,7 @@ def kernel_text(path, needle):
 
 
 def block_of(lines, packed=256):
+    """The unrolled block: packed = its v_pk_add_f32 count, None = whatever the fullest stretch has."""
     segs = [[]]
     for line in lines:
         t = line.strip()
@@ -49,7 +54,7 @@ def block_of(lines, packed=256):
             segs[-1].append(t)
     seg = max(segs, key=lambda s: sum(x.startswith("v_pk_add_f32") for x in s))
     n = sum(x.startswith("v_pk_add_f32") for x in seg)
-    if n != packed:
+    if packed is not None and n != packed:
         raise SystemExit(f"the fullest stretch has {n} v_pk_add_f32, not {packed}: the block is not unrolled in one piece")
     return seg
 
@@ -94,12 +99,36 @@ def check(path, kernel=HEADLINE, group_reads=1):
     return r
 
 
+def step2_figures(path, kernel=HEADLINE):
+    """The block's adds and moves; moves_in_steps: v_mov_b32 between a body's wait and its last v_cmpx."""
+    seg = block_of(kernel_text(path, kernel), packed=None)
+    in_steps, pending, waited = 0, 0, False
+    for t in seg:
+        if t.startswith("s_waitcnt") and "lgkmcnt" in t:
+            waited, pending = True, 0
+        elif waited and t.startswith("v_mov_b32"):
+            pending += 1
+        elif waited and t.startswith("v_cmpx"):
+            in_steps += pending
+            pending = 0
+    return {
+        "packed_adds": sum(t.startswith("v_pk_add_f32") for t in seg),
+        "plain_adds": sum(t.startswith("v_add_f32") for t in seg),
+        "moves": sum(t.startswith("v_mov_b32") for t in seg),
+        "moves_in_steps": in_steps,
+        "checks": sum(t.startswith("v_cmpx") for t in seg),
+    }
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("asm")
     p.add_argument("--kernel", default=HEADLINE)
     p.add_argument("--group-reads", type=int, default=1)
+    p.add_argument("--step2", action="store_true", help="print step2_figures() as well")
     a = p.parse_args()
+    if a.step2:
+        print(step2_figures(a.asm, a.kernel))
     r = check(a.asm, a.kernel, a.group_reads)
     print(r)
     return 0 if r["ok"] else 1
