@@ -91,35 +91,12 @@ constexpr uint32_t kDMaxSym = kDiagMaxSym;
 #ifndef SVH_DIAG_AB
 #define SVH_DIAG_AB 0
 #endif
-#ifndef SVH_DIAG_FINISH
-#define SVH_DIAG_FINISH 0
-#endif
 // SVH_DIAG_PAB (diagnostic builds of the path variant, timing only, wrong paths): 1 = no decision
 // bits, 2 = no ring writes and no folds (the light minima), 3 = no record stores at the blocks' ends
 // (words, checkpoints, F and sink checkpoints), 4 = one exec_collect and one fold per block (the ring
 // writes stay: against 2, the cost of the collects every 8 steps)
 #ifndef SVH_DIAG_PAB
 #define SVH_DIAG_PAB 0
-#endif
-// SVH_DIAG_CMPX2 (A/B of the two-diagonal step's check): 1 = v_cmpx as everywhere else, 0 = a compare
-// and an add with carry into a per-lane count, read at the row's end
-#ifndef SVH_DIAG_CMPX2
-#define SVH_DIAG_CMPX2 1
-#endif
-// SVH_DIAG_LDPRIO (A/B of the loader-wave variant): the step waves' s_setprio level, 0 = none (as
-// measured: raising them costs 3 % at 50 sequences and nothing at 13)
-#ifndef SVH_DIAG_LDPRIO
-#define SVH_DIAG_LDPRIO 0
-#endif
-// SVH_DIAG_LDDRAIN (A/B of the loader-wave variant): 1 = the step waves wait for their LDS reads
-// (lgkmcnt(0)) ahead of the block's barrier as the plain variant does, 0 = they do not
-#ifndef SVH_DIAG_LDDRAIN
-#define SVH_DIAG_LDDRAIN 1
-#endif
-// SVH_DIAG_QDMA (A/B of the quad ring's refill): 1 = one LDS-DMA instruction per symbol and group
-// (global_load_lds_dwordx4), 0 = a global load into registers and a 16-byte LDS write per symbol
-#ifndef SVH_DIAG_QDMA
-#define SVH_DIAG_QDMA 1
 #endif
 // SVH_DIAG_RDPLACE (A/B of the quad-ring kernels' two-step body, diag_body.h block()): 0 = the order
 // of every other instantiation, the body's reads at its top with the quads' address adds among them
@@ -293,43 +270,7 @@ void diag_set_kernel(const DiagSetEntry* __restrict__ e, const uint32_t* __restr
     }
 }
 
-// One workgroup per row after the main launch: the row's NR partials -> S, best state, the
-// violation flag; a row whose speculation failed is re-run here exactly (pipe_rerun_row).
-template <bool SX>
-__global__ __launch_bounds__(256) void diag_finish_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    uint32_t* flag = reinterpret_cast<uint32_t*>(lds + 2 * (size_t)m.P + 8);
-    if (tid < 64) {
-        float C = kInf, bv = kInf;
-        uint32_t bk = kNoRow, vi = 0;
-        for (uint32_t u = lane; u < m.nrng; u += 64) {
-            const uint64_t* pu = x.part + ((size_t)q * x.G + u) * 2;
-            const uint64_t a = pu[0], k2 = pu[1];
-            C = fminf(C, __builtin_bit_cast(float, (uint32_t)a));
-            vi |= (uint32_t)(a >> 32);
-            if (k2 != ~0ull) lex_min(bv, bk, lex_key_value(k2), lex_key_index(k2));
-        }
-        C = wave_min63(C);
-        wave_lexmin63(bv, bk);
-        const bool any = __builtin_amdgcn_ballot_w64(vi != 0) != 0;
-        if (lane == 63) {
-            float* out = b.scores + (size_t)q * m.n;
-            if (m.rowF >= 0) lex_min(bv, bk, out[m.rowF], (uint32_t)m.rowF);
-            if (m.rowS >= 0) {
-                out[m.rowS] = C;
-                lex_min(bv, bk, C, (uint32_t)m.rowS);
-            }
-            if (b.best) b.best[q] = bk == kNoRow ? -1 : (int64_t)bk;
-            x.viol[q] = any ? 1u : 0u;
-            *flag = any ? 1u : 0u;
-        }
-    }
-    __syncthreads();
-    if (*flag) pipe_rerun_row<2, 4, SX>(m, b, q, lds);
-}
-
-constexpr bool kVariants = SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0;  // (diagnostic builds keep the plain kernel)
+constexpr bool kVariants = SVH_DIAG_AB == 0;  // (diagnostic builds keep the plain kernel)
 
 template <int W, bool SX, bool PATHS = false, int DM = 1, bool LD = false, bool FL = false, bool QD = false>
 const void* kernel_fn() {
@@ -414,15 +355,7 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     FusedBatch bb = b;
     PipeScratch xx = x;
     void* args[] = {&mm, &bb, &xx};
-    const hipError_t e = launch_fn(fn, L.grid, L.threads, L.lds_request, args, stream);
-#if SVH_DIAG_FINISH
-    if (e != hipSuccess) return e;
-    const void* fin = m.sx ? reinterpret_cast<const void*>(&diag_finish_kernel<true>)
-                           : reinterpret_cast<const void*>(&diag_finish_kernel<false>);
-    return hipLaunchKernel(fin, dim3(b.nseq), dim3(256), args, (2 * (size_t)m.P + 8 + 1) * 4, stream);
-#else
-    return e;
-#endif
+    return launch_fn(fn, L.grid, L.threads, L.lds_request, args, stream);
 }
 
 hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out) {

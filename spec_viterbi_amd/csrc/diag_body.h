@@ -8,7 +8,7 @@
 // (the callee is simplified before it is inlined; 31 of 31 kernels differed), as text the existing
 // instantiations are instruction for instruction what they were (tools/asm_same.py).
     static_assert(DM == 1 || (DM == 2 && !PATHS), "decoded paths keep one diagonal per lane");
-    static_assert(!LD || (!PATHS && SVH_DIAG_AB == 0 && SVH_DIAG_FINISH == 0), "the loader wave: scores only");
+    static_assert(!LD || (!PATHS && SVH_DIAG_AB == 0), "the loader wave: scores only");
     static_assert(!FL || LD, "the floor is a loader-wave launch");
     static_assert(!QD || (DM == 2 && LD && !PATHS && !FL && kDK == 64),
                   "the quad ring: two diagonals per lane, the loader wave, scores only; a group is one wave's 64 x 16 bytes");
@@ -193,34 +193,15 @@
     // wave-instruction, lane l's 16 bytes from dtab4[o][c0 + l] to the wave-uniform base + 16 l; a group
     // that is the ring's first goes into the mirror behind the ring as well.  Wave wv of nw takes the
     // symbols o = wv, wv + nw, ...  Not waited for here.
-    // (SVH_DIAG_QDMA = 0, the A/B: through registers, global_load_dwordx4 and ds_write_b128.)
     auto qfill = [&](uint32_t g, uint32_t wv, uint32_t nw) {
         if constexpr (QD) {
             const uint32_t c0 = (rg * RW + g * kDK) % NP;
             const uint32_t s0 = (g % kDG) * kDK;
             const float4* src = m.dtab4 + c0 + lane;
-            if constexpr (SVH_DIAG_QDMA) {
-                for (uint32_t o = wv; o < S; o += nw) {
-                    const uint32_t d = ring_a + (o * kDRS + s0) * 16u;
-                    lds_dma16(src + (size_t)o * NP, d);
-                    if (s0 == 0) lds_dma16(src + (size_t)o * NP, d + kDR * 16u);
-                }
-            } else {
-                constexpr uint32_t kQB = 8;  // symbols per batch of loads
-                for (uint32_t o0 = wv; o0 < S; o0 += nw * kQB) {
-                    float4 v[kQB];
-#pragma unroll
-                    for (uint32_t r = 0; r < kQB; ++r) v[r] = src[(size_t)min(o0 + r * nw, S - 1) * NP];
-#pragma unroll
-                    for (uint32_t r = 0; r < kQB; ++r) {
-                        const uint32_t o = o0 + r * nw;
-                        if (o < S) {
-                            float* d = ring + ((size_t)o * kDRS + s0 + lane) * 4;
-                            *reinterpret_cast<float4*>(d) = v[r];
-                            if (s0 == 0) *reinterpret_cast<float4*>(d + kDR * 4) = v[r];
-                        }
-                    }
-                }
+            for (uint32_t o = wv; o < S; o += nw) {
+                const uint32_t d = ring_a + (o * kDRS + s0) * 16u;
+                lds_dma16(src + (size_t)o * NP, d);
+                if (s0 == 0) lds_dma16(src + (size_t)o * NP, d + kDR * 16u);
             }
         }
     };
@@ -449,7 +430,6 @@
     // DM = 2: the scores of the lane's two diagonals as one pair, their minimum in a pair of its own
     // (the source of the packed heavy terms)
     f2 X2 = (f2){xv, xv2};
-    uint32_t nviol = 0;  // (SVH_DIAG_CMPX2 = 0: steps at which the lane's check failed)
     auto step2 = [&](const float4& h, float xs, const f2& ea, const f2& eb) {
         XP.x = fminf(X2.x, X2.y);             // m: what the check and the sink need of the two scores
         const f2 Y = XP.xx + (f2){h.x, h.y};  // {A_F + m, A_S + m}
@@ -468,8 +448,7 @@
         } else {
             asm("v_pk_add_f32 %0, %0, %1\n\tv_min_f32 v95, v95, %2" : "+&{v[94:95]}"(FC) : "v"(hzw), "v"(Y.y));
         }
-        if (SVH_DIAG_CMPX2) check_off(Y.x, FC.x);
-        else nviol += Y.x < FC.x ? 1u : 0u;
+        check_off(Y.x, FC.x);
         X2 = (f2){fminf(zb.x, za.x), fminf(zb.y, za.y)};
 #else
         const f2 Wv = FC + (f2){h.z, h.w};    // {F' = X_FF + F, X_SS + c}
@@ -477,8 +456,7 @@
         const f2 zb = eb + X2;                // {eb_a + x_a, eb_b + x_b}
         float cn = fminf(Wv.y, Y.y);
         if (SX) cn = fminf(cn, xs + FC.x);    // X_SF + F
-        if (SVH_DIAG_CMPX2) check_off(Y.x, Wv.x);
-        else nviol += Y.x < Wv.x ? 1u : 0u;
+        check_off(Y.x, Wv.x);
         X2 = (f2){fminf(zb.x, za.x), fminf(zb.y, za.y)};
         FC = (f2){Wv.x, cn};
 #endif
@@ -732,8 +710,6 @@
             }
             return;  // (ends here: see the note on S_BARRIER above the kernel)
         }
-        // the step waves ahead of the loader wave that shares a SIMD with one of them
-        if (SVH_DIAG_LDPRIO) __builtin_amdgcn_s_setprio(SVH_DIAG_LDPRIO);
     }
     for (uint32_t k = 0; k < nbmax; ++k) {
         const uint32_t rem = k < nb ? nst - k * kDK : 0u;
@@ -742,22 +718,12 @@
         // 0.1934 ms; the per-block cost is the barrier and its LDS drain, profiles/r06_diag/)
         if constexpr (!LD) blockwork(k);
         if (k < nb) {
-#ifdef SVH_DIAG_SIMPLE  // diagnostics: every block through the plain steps (no software pipeline)
-            tail(k, rem >= kDK ? kDK : rem);
-#else
             if (full) block(k);
             else tail(k, rem);
-#endif
         }
-        // (LD, SVH_DIAG_LDDRAIN = 0: the bare barrier.  What a step wave has in flight here are the
-        // prefetches of the next block's first steps -- LDS returns in order, and every earlier read
-        // has been used -- into its stream buffer and ring groups, none of which the loader wave
-        // writes in the coming period: DESIGN.md 5l)
-        if (LD && !SVH_DIAG_LDDRAIN) asm volatile("s_barrier" ::: "memory");
-        else if (SVH_DIAG_AB != 3) lds_barrier();
+        if (SVH_DIAG_AB != 3) lds_barrier();
     }
 
-    if (DM == 2 && !SVH_DIAG_CMPX2) alive &= __builtin_amdgcn_ballot_w64(nviol == 0);
     F = FC.x;
     c = FC.y;
     xv = DM == 2 ? X2.x : XP.x;
@@ -767,29 +733,6 @@
 #if SVH_DIAG_AB == 5  // diagnostics: the scores only (every wave leaves here)
     if (real && m.lrow[(rg * 64 + lane + nst) % NP] != kNoRow)
         g_st_score(b.scores + (size_t)q * m.n + m.lrow[(rg * 64 + lane + nst) % NP], xv);
-    return;
-#endif
-#if SVH_DIAG_FINISH  // partials only: diag_finish_kernel combines them after this launch
-    if (real) {
-        float* out = b.scores + (size_t)q * m.n;
-        const uint32_t r = m.lrow[(rg * 64 + lane + nst) % NP];
-        float bv = kInf;
-        uint32_t bk = kNoRow;
-        if (r != kNoRow) {
-            out[r] = xv;
-            bv = xv;
-            bk = r;
-        }
-        wave_lexmin63(bv, bk);
-        const float cmin = wave_min63(c);
-        const bool any_viol = alive != ~0ull;
-        if (lane == 63) {
-            uint64_t* part = x.part + ((size_t)q * x.G + rg) * 2;
-            part[0] = ((uint64_t)(any_viol ? 1u : 0u) << 32) | __builtin_bit_cast(uint32_t, cmin);
-            part[1] = lex_key(bv, bk);
-            if (rg == 0 && m.rowF >= 0) out[m.rowF] = F;
-        }
-    }
     return;
 #endif
     uint32_t last = 0;

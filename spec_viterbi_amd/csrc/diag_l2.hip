@@ -37,12 +37,11 @@
 //     {fl(X_FF(s2) + X_FF(s1)), fl(X_SS(s2) + X_SS(s1)), fl(X_FF(s2) + A_F(s1)), fl(X_SS(s2) + A_S(s1))},
 //     {A_F(s2), A_S(s2), X_FF(s1), A_F(s1)}, {ring address of (s2, column), of (s1, column - 1)}
 // so the F and S halves of a term share an operand register (as one packed add they measured 5 %
-// slower than as two single adds, SVH_DL2_PK).  A check is one v_cmpx, as at level 0: a
+// slower than as two single adds).  A check is one v_cmpx, as at level 0: a
 // lane that fails switches itself off until the block's end, where the wave notes which lanes are
-// left (SVH_DL2_CMPX = 0: a compare and an add with carry into a per-lane count); one barrier per
-// block.  In a full block the reads are issued ahead of their use (the stream entry kPS chunks, the
-// ring pairs kPE chunks): the pairs' addresses come from the entry, two LDS round trips that the
-// plain form paid per chunk.
+// left; one barrier per block.  In a full block the reads are issued ahead of their use (the stream
+// entry kPS chunks, the ring pairs kPE chunks): the pairs' addresses come from the entry, two LDS
+// round trips that the plain form paid per chunk.
 //
 // A row's nch = (len - 1) / 2 chunks start from the first observation's state in b.v_in (row q) and
 // end in b.scores (row q); rows of 0 chunks are copied through.  The last wave of a row to arrive
@@ -81,18 +80,13 @@ static_assert(kPE >= 1 && kPE < kPS && kPS < kLB, "prefetch distances");
 __device__ __forceinline__ f2 lds_ld2(uint32_t a) {
     return *(const __attribute__((address_space(3))) f2*)(size_t)a;
 }
-// SVH_DL2_CMPX (A/B): 1 = a check is one v_cmpx (diag.hip's check_off / exec_collect: a lane that
-// fails switches itself off until the block's end), 0 = a compare and an add with carry into a count
-#ifndef SVH_DL2_CMPX
-#define SVH_DL2_CMPX 1
-#endif
 // EXEC &= !(a < b); see diag.hip: the chunks between two exec_collect() calls are straight-line
 // code or a wave-uniform loop, fenced off from the all-lanes code around them
-[[maybe_unused]] __device__ __forceinline__ void check_off(float a, float b) {
+__device__ __forceinline__ void check_off(float a, float b) {
     asm volatile("v_cmpx_nlt_f32_e32 vcc, %0, %1" : : "v"(a), "v"(b) : "vcc");
 }
 // alive &= EXEC; EXEC = all lanes (s_nop 4: five wait states between a write of EXEC and a DPP operation)
-[[maybe_unused]] __device__ __forceinline__ void exec_collect(uint64_t& alive) {
+__device__ __forceinline__ void exec_collect(uint64_t& alive) {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_and_b64 %0, %0, exec\n\t"
                  "s_mov_b64 exec, -1\n\t"
@@ -102,19 +96,11 @@ __device__ __forceinline__ f2 lds_ld2(uint32_t a) {
                  : "scc", "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-// SVH_DL2_PK (A/B): 1 = the F and S halves of a term as one v_pk_add_f32, 0 = single adds
-#ifndef SVH_DL2_PK
-#define SVH_DL2_PK 0
-#endif
-// (an asm statement: the compiler's SLP pass would pack two adjacent adds again)
-[[maybe_unused]] __device__ __forceinline__ float add1(float a, float b) {
+// One add kept single (an asm statement: the compiler's SLP pass would pack two adjacent adds again)
+__device__ __forceinline__ float add1(float a, float b) {
     float r;
     asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-}
-// n += [a < b] per lane: compare into VCC, add with carry-in (pipe_kernel.h step2's form)
-[[maybe_unused]] __device__ __forceinline__ void count_lt(uint32_t& n, float a, float b) {
-    asm volatile("v_cmp_lt_f32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, 0, %0, vcc" : "+v"(n) : "v"(a), "v"(b) : "vcc");
 }
 
 __host__ __device__ constexpr size_t diag_l2_lds(uint32_t W, uint32_t S) {
@@ -249,30 +235,13 @@ void diag_l2_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
     nbmax = (uint32_t)uniform((int)nbmax);
 
     f2 FC = (f2){F, c};  // the feeder and the lane's sink partial: one packed add advances both
-    uint32_t viol = 0;   // chunks at which one of the lane's checks failed
-    uint64_t alive = ~0ull;  // (SVH_DL2_CMPX: lanes whose checks have held so far, collected after every block)
+    uint64_t alive = ~0ull;  // lanes whose checks have held so far, collected after every block
     const float emax2 = m.emax2;
     const uint32_t lane8 = lane * 8u;
-    auto check = [&](float a, float b) {  // the lane fails where a < b
-        if constexpr (SVH_DL2_CMPX) check_off(a, b);
-        else count_lt(viol, a, b);
-    };
     // one chunk from its stream entry {ka, kb} and its two ring pairs
     auto compute = [&](const float4& ka, const float4& kb, const f2& E2, const f2& E1) {
         // E2 = {ea_p(s2), eb_p(s2)}, E1 = {ea_q(s1), eb_q(s1)}, q = p - 1
-#if SVH_DL2_PK
-        const f2 XX = (f2){xv, xv}, FF = FC.xx;
-        // the light position
-        const f2 t = E2.yy + E1.yx;                   // {eb_p(s2) + eb_q(s1), eb_p(s2) + ea_q(s1)}
-        const float fx = E2.x + kb.z;                 // ea_p(s2) + X_FF(s1)
-        const float xa = fminf(t.y, fx) + FC.x;
-        const float xb = t.x + xv;
-        // F's and S's rows, {F half, S half}
-        const f2 KF = (f2){ka.x, ka.y} + FC;          // {F' (speculated), (S, S)}
-        const f2 KM = (f2){ka.z, ka.w} + XX;          // (F, m), (S, m)
-        const f2 QB = ((f2){kb.x, kb.y} + E1.yy) + XX;  // (q, q-1)
-        const f2 QA = ((f2){kb.x, kb.y} + E1.xx) + FF;  // (q, F)
-#else  // the same adds one by one (add1: kept from the compiler's own packing)
+        // the adds one by one (add1: kept from the compiler's own packing)
         const f2 t = (f2){add1(E2.y, E1.y), add1(E2.y, E1.x)};
         const float fx = add1(E2.x, kb.z);
         const float xa = add1(fminf(t.y, fx), FC.x);
@@ -281,14 +250,13 @@ void diag_l2_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         const f2 KM = (f2){add1(ka.z, xv), add1(ka.w, xv)};
         const f2 QB = (f2){add1(add1(kb.x, E1.y), xv), add1(add1(kb.y, E1.y), xv)};
         const f2 QA = (f2){add1(add1(kb.x, E1.x), FC.x), add1(add1(kb.y, E1.x), FC.x)};
-#endif
         const float nm = fminf(KM.x, fminf(QB.x, QA.x));
-        check(nm, KF.x);
+        check_off(nm, KF.x);  // the lane fails where nm < F'
         // the margin bound of the light rows' (F, m) term
         const float Rf = kb.z + FC.x;
         const float thr = Rf + (emax2 + Rf) * 0x1p-20f;
         const float Lf = kb.w + xv;
-        check(Lf, thr);
+        check_off(Lf, thr);
         const float cn = fminf(fminf(KF.y, KM.y), fminf(QB.y, QA.y));
         xv = fminf(xa, xb);
         FC = (f2){KF.x, cn};
@@ -343,15 +311,15 @@ void diag_l2_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         if (k < nb) {
             const uint32_t rem = nch - k * kLB;
             const uint32_t e0 = (w * 2 + (k & 1u)) * kLB;
-            // (SVH_DL2_CMPX: the collect right behind the chunks -- straight-line code or a loop with a
+            // (the collect right behind the chunks -- straight-line code or a loop with a
             // scalar branch -- so that no other branch sees a partial EXEC)
             if (rem >= kLB) {
                 block(e0);
-                if constexpr (SVH_DL2_CMPX) exec_collect(alive);
+                exec_collect(alive);
             } else {
                 __builtin_amdgcn_sched_barrier(0);
                 for (uint32_t j = 0; j < rem; ++j) chunk(e0 + j);
-                if constexpr (SVH_DL2_CMPX) exec_collect(alive);
+                exec_collect(alive);
             }
         }
         lds_barrier();
@@ -364,7 +332,7 @@ void diag_l2_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
         const uint32_t r = m.lrow[(rg * 64 + lane + 2 * (nch % NP)) % NP];
         if (r != kNoRow) g_st_score(out + r, xv);  // the re-run and the tail may come from another XCD
         const float cmin = wave_min63(FC.y);
-        const bool any_viol = SVH_DL2_CMPX ? alive != ~0ull : __builtin_amdgcn_ballot_w64(viol != 0) != 0;
+        const bool any_viol = alive != ~0ull;
         if (lane == 63) {
             g_st64(x.part + ((size_t)q * x.G + rg) * 2, ((uint64_t)(any_viol ? 1u : 0u) << 32) | __builtin_bit_cast(uint32_t, cmin));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -63,7 +63,7 @@ __device__ __forceinline__ void pipe_reset_counters(const PipeScratch& x) {
     __hip_atomic_store(x.ctr + 2, ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// hwreg(HW_REG_XCC_ID, 0, 4): the XCD this wave runs on (the XCD-local hand-offs, SVH_PIPE_XL)
+// hwreg(HW_REG_XCC_ID, 0, 4): the XCD this wave runs on (the XCD-local hand-offs)
 __device__ __forceinline__ uint32_t xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFu; }
 
 }  // namespace pipe_dev

@@ -51,22 +51,13 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr uint32_t kR = kPipeRing;
 
 // Granule hand-off between workgroups: groups of 8 granules the consumer keeps in flight ahead of
-// use (1, 2 or 4), and the step of the next group at which the producer stores a finished group's
-// granules (0: at the end of the next group).  A/B knobs (tools/ab_build.sh -D...).
-#ifndef SVH_PIPE_GPF
-#define SVH_PIPE_GPF 2
-#endif
-#ifndef SVH_PIPE_GST
-#define SVH_PIPE_GST 2
-#endif
-constexpr uint32_t kGpf = SVH_PIPE_GPF;
+// use, and the step of the next group at which the producer stores a finished group's granules.
+constexpr uint32_t kGpf = 2;
 // (Round 5, measured and not kept: four groups for a consumer whose producer sits on another XCD.
 // The cross-XCD rows, 2 of the headline's 50, end the launch 15-25 us after the XCD-local ones; with
 // four groups in flight their prefetches outran the producer and polled: 0.296-0.306 ms against
 // 0.250-0.254, profiles/r05_s8.)
-constexpr uint32_t kGst = SVH_PIPE_GST;
-static_assert(kGpf == 1 || kGpf == 2 || kGpf == 4, "granule prefetch depth");
-static_assert(kGst < 8, "granule store step");
+constexpr uint32_t kGst = 2;
 
 // LDS boundary ring layout: 0 = [u][lane] (every step stores its row, one ds_write_b32; TM = 0,
 // pipe.hip); 1 = [u / 8][lane][u % 8]: a group's 8 last-slot scores stay in registers and go out as
@@ -86,18 +77,15 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// LDS reads of the exchange kept where they are issued (A/B knob SVH_PIPE_LDSX, default 1; within
+// LDS reads of the exchange kept where they are issued (within
 // run-to-run noise on the headline, 0.258-0.265 vs 0.256-0.264 ms, profiles/r04_s9/ab.log): the
 // compiler otherwise (a) hoisted the slow path's re-load of the next group's boundary vector out of
 // its branch, so every group re-read it at its first use and waited for it there, and (b) moved the
 // readfirstlane of the neighbours' counts (read four steps before their use) up to the reads,
 // waiting for them at once.  An opaque zero in the slow path's address and an asm use of each count
 // where it is needed keep both reads' latency behind steps.
-#ifndef SVH_PIPE_LDSX
-#define SVH_PIPE_LDSX 1
-#endif
 
-// XCD-local hand-offs (A/B knob SVH_PIPE_XL): every workgroup publishes its XCC id; a granule
+// XCD-local hand-offs: every workgroup publishes its XCC id; a granule
 // producer whose consumer workgroup sits on the same XCD stores its granules with plain stores
 // (kept in the XCD's L2) instead of agent-scope write-through stores (which drop the line, so the
 // consumer's L2-served load goes to the fabric), and a consumer on its producer's XCD does the same
@@ -105,20 +93,14 @@ __device__ __forceinline__ void wait_vmcnt() {
 // by the L2 the plain store wrote); a pair on different XCDs, or one whose id is not known yet,
 // keeps write-through stores.  Measured on the headline: 0.248-0.251 ms against 0.258-0.265
 // (profiles/r04_s9/ab.log); the XCD half whose hops were slow (§5f) comes down to the other's rate.
-#ifndef SVH_PIPE_XL
-#define SVH_PIPE_XL 1
-#endif
 
 // The next group's boundary vector (SRC 1) read at step 4, right after the producer's count it is
-// validated against (A/B knob SVH_PIPE_EARLYV): LDS executes one CU's instructions in order and the
+// validated against: LDS executes one CU's instructions in order and the
 // producer wrote its ring before its count, so a count that covers the group guarantees the vector
 // read issued after it sees the group; otherwise the slow path waits and reads it again.  At the
-// group's end (0) the read's latency sat in front of the next group's second step.
-#ifndef SVH_PIPE_EARLYV
-#define SVH_PIPE_EARLYV 1
-#endif
+// group's end the read's latency sat in front of the next group's second step.
 
-// Exchange helpers (A/B knob SVH_PIPE_XHELP, workgroups of three waves or more): the vector-memory
+// Exchange helpers (workgroups of three waves or more): the vector-memory
 // counter retires a wave's loads and stores in issue order, so a wave that both stores to another
 // XCD (write-through, acknowledged late) and waits for a load waits for those stores too.  The
 // granule reader (wave 0) published its progress word and the granule writer (wave W - 1) loaded
@@ -126,18 +108,13 @@ __device__ __forceinline__ void wait_vmcnt() {
 // observations.  With the helpers wave 1, which has no other global traffic, publishes the progress
 // (its own, never ahead of wave 0's) and wave W - 2 loads the consumer's word once per 32
 // observations into an LDS slot that wave W - 1 reads: wave 0 only loads and wave W - 1 only stores.
-#ifndef SVH_PIPE_XHELP
-#define SVH_PIPE_XHELP 1
-#endif
 
-// Step of a group at which the neighbours' counts (and, SVH_PIPE_EARLYV, the next group's vector)
-// are read (A/B knob SVH_PIPE_CNTSTEP, 1..7): later reads see a producer further ahead, so the next
+// Step of a group at which the neighbours' counts (and the next group's vector)
+// are read (1..7): later reads see a producer further ahead, so the next
 // group's vector is valid more often, at the price of less time to hide the LDS latency.  Headline
 // kernel (profiles/r05_xhelp/ab_cntstep.log): step 4 0.2296-0.2329 ms, 5 0.2283-0.2291, 6
 // 0.2284-0.2295, 7 0.243-0.252 (the read's latency no longer hidden).
-#ifndef SVH_PIPE_CNTSTEP
-#define SVH_PIPE_CNTSTEP 5
-#endif
+constexpr uint32_t kCntStep = 5;
 // (Round 5, measured and not kept: the pair tables' compiler barrier placed after the prologue's
 // other loads, so the heavy constants, the first state and the symbol windows load while the tables
 // are in flight.  The first sweep started later, not earlier (7.2 us after the launch's first entry
@@ -152,7 +129,6 @@ __device__ __forceinline__ void wait_vmcnt() {
 // with the producer's whole first group.  The sweeps start earlier but the rows end no sooner (the
 // workgroup hop's lag is set by the groups' hand-off, not by the start) and the early prefetches
 // poll: 0.2307-0.2323 ms against 0.2291-0.2299, profiles/r05_xhelp/ab_gfirst.log.)
-static_assert(SVH_PIPE_CNTSTEP >= 1 && SVH_PIPE_CNTSTEP <= 7, "count step");
 
 // Diagnostic ablation (-DSVH_PIPE_NOWAIT, timing only, wrong results): every exchange operation
 // runs, but no wait on a neighbour does (counts, flow control, granule tags and progress words are
@@ -182,38 +158,26 @@ constexpr bool kNoPRing = true;
 constexpr bool kNoPRing = false;
 #endif
 
-// Slow-path loads that wait for themselves (SVH_PIPE_SYNCSLOW, default 1): the compiler tracks every
+// Slow-path loads that wait for themselves: the compiler tracks every
 // load it emits, so a poll loop's reload left pending where the slow path rejoins the body made it
 // drain every outstanding operation there -- on the fast path too: the granule consumer's body then
 // waited with vmcnt(0) for the next group's prefetch once per group, and the LDS consumers'
 // re-read of a boundary vector forced an lgkmcnt wait behind the ring stores.  A load whose wait is
 // inside its own asm leaves nothing for the compiler to drain (the wide kernel's g_ld64_sync).
-#ifndef SVH_PIPE_SYNCSLOW
-#define SVH_PIPE_SYNCSLOW 1
-#endif
 __device__ __forceinline__ uint64_t g_ld64_slow(const uint64_t* p) {
-    if constexpr (SVH_PIPE_SYNCSLOW) {
-        uint64_t r;
-        asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(r) : "v"(p) : "memory");
-        return r;
-    }
-    return g_ld64(p);
+    uint64_t r;
+    asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(r) : "v"(p) : "memory");
+    return r;
 }
 __device__ __forceinline__ uint32_t lds_ld32_slow(const uint32_t* p) {
-    if constexpr (SVH_PIPE_SYNCSLOW) {
-        uint32_t r;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_addr(p)) : "memory");
-        return r;
-    }
-    return lds_ld32(p);
+    uint32_t r;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_addr(p)) : "memory");
+    return r;
 }
 __device__ __forceinline__ float lds_ldf_slow(const float* p) {
-    if constexpr (SVH_PIPE_SYNCSLOW) {
-        float r;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_addr(p)) : "memory");
-        return r;
-    }
-    return *p;
+    float r;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_addr(p)) : "memory");
+    return r;
 }
 
 // One lane's LDS store of a wave-uniform word (a wave's count): EXEC narrowed to lane 0 inside the
@@ -497,7 +461,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
     // sets it when the launch fits the chip at one workgroup per CU, the grid padded to a multiple
     // of 8): per-class tickets, so that a row's G workgroups share an XCD class (blocks b and b + 8
     // share an XCD under the observed round-robin placement; speed only -- the hand-offs check the
-    // real XCC ids, SVH_PIPE_XL).  Every class r = b % 8 holds n = N / 8 blocks and takes f = n / G
+    // real XCC ids).  Every class r = b % 8 holds n = N / 8 blocks and takes f = n / G
     // rows whole: its k-th ticket (k < f G) is member k % G of row r f + k / G, members numbered in
     // start order.  The n - f G spare tickets of the classes form the remaining rows from one more
     // counter, also in start order (slot u is member u % G of row 8 f + u / G), so every member's
@@ -535,11 +499,9 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
         return;
     }
     const uint32_t ep = (uint32_t)uniform((int)__hip_atomic_load(x.ctr + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
-#if SVH_PIPE_XL
     const uint32_t my_xcc = (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFu;  // hwreg(HW_REG_XCC_ID, 0, 4)
     if (tid == 0 && x.xcc)
         __hip_atomic_store(x.xcc + (size_t)q * G + g, (ep << 4) | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 
     const uint8_t* __restrict__ sym = b.symbols + b.sym_off[q];
     // L2: the sweep's t runs over observations 1 .. 2 nch of the nch = (L - 1) / 2 chunks (every row
@@ -810,11 +772,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
         // head's cost adds up along the chain of waves).  What is indexed by the position in the
         // cycle of 32 -- symbol windows, LDS ring slots -- uses u = t - tb; counts, granules and
         // tags use t.
-#ifdef SVH_PIPE_HEAD  // A/B diagnostic: the head of single observations of before
-        const uint32_t tb = 0u;
-#else
         const uint32_t tb = PATHS ? 0u : (first & 31u);
-#endif
         auto load_window_raw = [&](uint32_t wi) -> uint4 {  // lane l: symbols of u = 1024 wi + 16 l ..
             const uint32_t off = wi * kPipeWindow + lane * 16 + tb;
             if ((tb & 15u) == 0)
@@ -1138,9 +1096,9 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
         uint64_t* const gout = x.gran + ((size_t)q * (G - 1) + g) * kGR;       // dst == 2
         uint64_t* const cons_in = reinterpret_cast<uint64_t*>(x.cons) + (size_t)q * G + g;      // src == 2 publishes
         const uint64_t* const cons_out = reinterpret_cast<const uint64_t*>(x.cons) + (size_t)q * G + g + 1;  // dst == 2 reads
-        // SVH_PIPE_XHELP: wave 1 publishes this workgroup's progress (helped: wave 0 does not), wave
+        // Exchange helpers: wave 1 publishes this workgroup's progress (helped: wave 0 does not), wave
         // W - 2 forwards the consumer's word to wave W - 1 through consf (cnt[14..15])
-        constexpr bool kXh = SVH_PIPE_XHELP && W >= 3;
+        constexpr bool kXh = W >= 3;
         static_assert(W <= 14, "cnt[14..15] holds the forwarded progress word");
         uint64_t* const consf = reinterpret_cast<uint64_t*>(cnt + 14);
         const bool helped = kXh && g > 0 && g * W + 1 < m.nblk;
@@ -1150,10 +1108,9 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
     float bprev2 = kInf;  // L2: ... of t-2 (a chunk's step reads the previous block's two last scores)
 
         auto give_up = [&]() -> bool { return ++spins > kSpinLimit; };
-        // SVH_PIPE_XL: is workgroup og of this row on this wave's XCD?  (bounded poll of its id; not
+        // XCD-local hand-offs: is workgroup og of this row on this wave's XCD?  (bounded poll of its id; not
         // known in time: no, i.e. write-through stores, always correct)
         auto xcc_local = [&](uint32_t og) -> bool {
-#if SVH_PIPE_XL
             if (!x.xcc) return false;
             const uint32_t* p = x.xcc + (size_t)q * G + og;
             for (int i = 0; i < 32; ++i) {
@@ -1161,20 +1118,18 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                 if ((wv >> 4) == (ep & 0x0FFFFFFFu)) return (wv & 0xFu) == my_xcc;
                 __builtin_amdgcn_s_sleep(4);
             }
-#endif
-            (void)og;
             return false;
         };
         bool gran_plain = false, cons_plain = false;
-        // granule / progress-word stores: plain when the reader shares this XCD (SVH_PIPE_XL)
+        // granule / progress-word stores: plain when the reader shares this XCD
         // (a plain store is a relaxed atomic store at wavefront scope: the same unflagged
         // global_store as `*a = v64`, but one the compiler may not tear, merge or sink)
         auto st_gran = [&](uint64_t* a, uint64_t v64) {
-            if (SVH_PIPE_XL && gran_plain) __hip_atomic_store(a, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (gran_plain) __hip_atomic_store(a, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             else g_st64(a, v64);
         };
         auto st_cons = [&](uint64_t v64) {
-            if (SVH_PIPE_XL && cons_plain) __hip_atomic_store(cons_in, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (cons_plain) __hip_atomic_store(cons_in, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             else g_st64(cons_in, v64);
         };
         // wait until the previous wave has published observations < need
@@ -1293,9 +1248,9 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                 }
             };
 
-            if constexpr (SVH_PIPE_XL && DST == 2) gran_plain = xcc_local(g + 1);
-            if constexpr (SVH_PIPE_XL && SRC == 2) cons_plain = xcc_local(g - 1);
-            if constexpr (SVH_PIPE_XL && SRC == 1 && kXh) {
+            if constexpr (DST == 2) gran_plain = xcc_local(g + 1);
+            if constexpr (SRC == 2) cons_plain = xcc_local(g - 1);
+            if constexpr (SRC == 1 && kXh) {
                 if (hpub) cons_plain = xcc_local(g - 1);
             }
             // publish the state at first-1 and fetch the boundary of first-1 (L2: first - 1 = 0 is
@@ -1322,7 +1277,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
             uint32_t t = first;
             unsigned long long c0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
             SVH_RT(9);
-            // head: single observations up to the first group of 32 (none unless tb is forced to 0)
+            // head: single observations up to the first group of 32 (none unless tb is 0: the path variants)
             for (; t < len && ((t - tb) & 31u); ++t) single(t);
             if (dbg) {
                 const unsigned long long c1 = __builtin_amdgcn_s_memtime();
@@ -1341,7 +1296,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                 uint32_t gpend_t = 0;  // read back from the ring one group before they are stored
                 uint64_t cons_v = 0;   // DST 2: prefetched progress word of the consumer
                 if constexpr (DST == 2) cons_v = g_ld64(cons_out);
-                uint64_t cons_h = 0;   // SVH_PIPE_XHELP, wave W - 2: the word loaded for consf
+                uint64_t cons_h = 0;   // exchange helpers, wave W - 2: the word loaded for consf
                 if constexpr (DST == 1 && kXh) {
                     if (hrd) cons_h = g_ld64(cons_out);
                 }
@@ -1355,7 +1310,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                 // SRC 1: the next group's vector, loaded at the end of every group (stale unless
                 // next_ok) into this one loop-carried register, re-loaded there when it was stale
                 float bv_next = kInf;
-                float bv_spec = kInf;  // SVH_PIPE_EARLYV: the next group's vector read at step 4
+                float bv_spec = kInf;  // the next group's vector read at step 4
                 bool next_ok = false;
                 if constexpr (SRC == 1) bv_next = ring_prev[ring_idx(lane & 7u, 63)];  // group at t (u % 32 == 0)
                 while (t + 32 <= len) {
@@ -1404,7 +1359,7 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                             prefetch(gq[j % GPF], gin + ((tg + 8 * GPF + (lane & 7u)) & (kGR - 1)));
                         }
                         if constexpr (DST == 1) {
-                            if constexpr (SVH_PIPE_LDSX) asm volatile("" : "+v"(nc_rd));
+                            asm volatile("" : "+v"(nc_rd));
                             if ((int)uniform((int)nc_rd) < (int)tg + 8 - (int)kR) wait_next((int)tg + 8 - (int)kR);
                         }
                         auto one = [&](auto kc) {
@@ -1413,8 +1368,8 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                             if constexpr (SRC == 1 && k == 1) {  // step 0 used only the previous vector
                                 if (!next_ok) {  // the producer had not published this group: wait, re-load
                                     if (dbg) ++dg[14];
-                                    uint32_t z = 0;  // SVH_PIPE_LDSX: an address the compiler cannot hoist
-                                    if constexpr (SVH_PIPE_LDSX) asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+                                    uint32_t z;  // an address the compiler cannot hoist
+                                    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
                                     wait_prev(tg + 8);
                                     asm volatile("" ::: "memory");
                                     bv_next = lds_ldf_slow(ring_prev + ring_idx(8 * j + (lane & 7u), 63) + z);
@@ -1447,20 +1402,20 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                             paths_after(tg + k, std::bool_constant<j == 0 && k == 0>{},
                                         std::bool_constant<k == 0 && (j == 0 || j == 2)>{},
                                         std::bool_constant<j == 3 && k == 7>{}, std::integral_constant<uint32_t, k & 3u>{});
-                            if constexpr (k == SVH_PIPE_CNTSTEP) {  // the counts checked at the end of the group
+                            if constexpr (k == kCntStep) {  // the counts checked at the end of the group
                                 asm volatile("" ::: "memory");
                                 if constexpr (SRC == 1) pc_rd = lds_ld32(cnt_w - 1);
                                 if constexpr (DST == 1) nc_rd = lds_ld32(cnt_w + 1);
-                                if constexpr (SRC == 1 && SVH_PIPE_EARLYV) {  // after the count it is checked against
+                                if constexpr (SRC == 1) {  // after the count it is checked against
                                     asm volatile("" ::: "memory");
                                     bv_spec = ring_prev[ring_idx(((8 * j + 8) & (kR - 1)) + (lane & 7u), 63)];
                                 }
-                                // SVH_PIPE_LDSX: issued here, not where the scheduler would sink them (the
+                                // issued here, not where the scheduler would sink them (the
                                 // group's end, right before their use)
-                                if constexpr (SVH_PIPE_LDSX) __builtin_amdgcn_sched_barrier(0);
+                                __builtin_amdgcn_sched_barrier(0);
                             }
-                            if constexpr (SVH_PIPE_LDSX && SVH_PIPE_RING8 && k == 3) __builtin_amdgcn_sched_barrier(0);
-                            if constexpr (DST == 2 && kGst != 0 && k == kGst) {  // the last group's granules
+                            if constexpr (SVH_PIPE_RING8 && k == 3) __builtin_amdgcn_sched_barrier(0);
+                            if constexpr (DST == 2 && k == kGst) {  // the last group's granules
                                 if (gpend_t && lane < 8)
                                     st_gran(gout + ((gpend_t + lane) & (kGR - 1)),
                                            ((uint64_t)gtag(ep, gpend_t) << 32) | __builtin_bit_cast(uint32_t, gpend));
@@ -1479,19 +1434,12 @@ __global__ __launch_bounds__(64 * W) void pipe_viterbi_kernel(PipeModel m, Fused
                         asm volatile("" ::: "memory");
                         put_cnt(tg + 8);
                         if constexpr (SRC == 1) {  // the next group's boundary vector (valid if next_ok)
-                            if constexpr (SVH_PIPE_LDSX) asm volatile("" : "+v"(pc_rd));
+                            asm volatile("" : "+v"(pc_rd));
                             next_ok = kNoWait || (uint32_t)uniform((int)pc_rd) >= tg + 16;
                             asm volatile("" ::: "memory");
-                            if constexpr (SVH_PIPE_EARLYV) bv_next = bv_spec;
-                            else bv_next = ring_prev[ring_idx(((8 * j + 8) & (kR - 1)) + (lane & 7u), 63)];
+                            bv_next = bv_spec;
                         }
                         if constexpr (DST == 2) {
-                            // granules of the previous group (read back from the ring one group ago)
-                            if constexpr (kGst == 0) {
-                                if (gpend_t && lane < 8)
-                                    st_gran(gout + ((gpend_t + lane) & (kGR - 1)),
-                                           ((uint64_t)gtag(ep, gpend_t) << 32) | __builtin_bit_cast(uint32_t, gpend));
-                            }
                             gpend = ring_w[ring_idx(8 * j + (lane & 7u), 63)];
                             gpend_t = tg;
                         }

@@ -25,7 +25,7 @@
 // r = b % 8 (blocks b and b + 8 share an XCD under the observed round-robin placement), whose
 // tickets map to a contiguous range of sequence groups, so a group's nblk workgroups share an L2.
 // Each workgroup publishes its XCC id; a granule producer whose consumer is on its own XCD stores
-// with plain (L2-resident) stores, and so does a consumer with its progress word (SVH_PIPEW_XL);
+// with plain (L2-resident) stores, and so does a consumer with its progress word;
 // otherwise, or when the other's id is not known in time, agent-scope write-through stores.  Per
 // class the tickets are still taken in start order, so a consumer's producer has always started.
 // Each wave combines its own lanes (S partial, argmin, violation); the last wave of a sequence
@@ -41,13 +41,6 @@
 // shuffles) and lanes 0..7 store prec[block][t].  pipe_paths.hip walks the paths from them.
 #pragma once
 #include "pipe_common.h"
-
-// XCD classes and XCD-local hand-offs for the wide plan (A/B knobs; header comment): the launch's
-// row mapping (PipeScratch::xmap, launch_pipew; SVH_PIPEW_XMAP=0 at run time turns it off) and the
-// plain stores between workgroups on one XCD.
-#ifndef SVH_PIPEW_XL
-#define SVH_PIPEW_XL 1
-#endif
 
 namespace svh {
 
@@ -131,11 +124,9 @@ __global__ __launch_bounds__(64 * W) void pipew_viterbi_kernel(PipeModel m, Fuse
     __syncthreads();
     const uint32_t ep = (uint32_t)uniform((int)__hip_atomic_load(x.ctr + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
     const uint32_t q = qg * W + w;
-#if SVH_PIPEW_XL
     const uint32_t my_xcc = xcc_id();
     if (tid == 0 && x.xcc && qg * W < b.nseq)
         __hip_atomic_store(x.xcc + (size_t)qg * nblk + blk, (ep << 4) | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 
     if (q < b.nseq) {
         const uint8_t* __restrict__ sym = b.symbols + b.sym_off[q];
@@ -373,10 +364,9 @@ __global__ __launch_bounds__(64 * W) void pipew_viterbi_kernel(PipeModel m, Fuse
                 c = g_ld64_sync(cons_out);
             }
         };
-        // SVH_PIPEW_XL: is block ob of this group on this wave's XCD?  (a bounded poll of its id; not
+        // XCD-local hand-offs: is block ob of this group on this wave's XCD?  (a bounded poll of its id; not
         // known in time: no, i.e. write-through stores, always correct)
         auto xcc_local = [&](uint32_t ob) -> bool {
-#if SVH_PIPEW_XL
             if (!x.xcc) return false;
             const uint32_t* p = x.xcc + (size_t)qg * nblk + ob;
             for (int i = 0; i < 32; ++i) {
@@ -384,19 +374,17 @@ __global__ __launch_bounds__(64 * W) void pipew_viterbi_kernel(PipeModel m, Fuse
                 if ((wv >> 4) == (ep & 0x0FFFFFFFu)) return (wv & 0xFu) == my_xcc;
                 __builtin_amdgcn_s_sleep(4);
             }
-#endif
-            (void)ob;
             return false;
         };
         bool gran_plain = false, cons_plain = false;
         // granule / progress-word stores: plain (a relaxed wavefront-scope atomic store: the same
         // unflagged global_store, kept in this XCD's L2) when the reader shares this XCD
         auto st_gran = [&](uint64_t* a, uint64_t v64) {
-            if (SVH_PIPEW_XL && gran_plain) __hip_atomic_store(a, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (gran_plain) __hip_atomic_store(a, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             else g_st64(a, v64);
         };
         auto st_cons = [&](uint64_t v64) {
-            if (SVH_PIPEW_XL && cons_plain) __hip_atomic_store(cons_in, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (cons_plain) __hip_atomic_store(cons_in, v64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             else g_st64(cons_in, v64);
         };
         auto put_gran1 = [&](uint32_t s, float val) {
@@ -407,8 +395,8 @@ __global__ __launch_bounds__(64 * W) void pipew_viterbi_kernel(PipeModel m, Fuse
         auto sweep = [&](auto srcc, auto dstc) {
             constexpr int SRC = decltype(srcc)::value, DST = decltype(dstc)::value;
             using I0 = std::integral_constant<int, 0>;
-            if constexpr (SVH_PIPEW_XL && DST == 2) gran_plain = xcc_local(blk + 1);
-            if constexpr (SVH_PIPEW_XL && SRC == 2) cons_plain = xcc_local(blk - 1);
+            if constexpr (DST == 2) gran_plain = xcc_local(blk + 1);
+            if constexpr (SRC == 2) cons_plain = xcc_local(blk - 1);
             // one observation outside the body (head, tail): per-observation exchange
             auto single = [&](uint32_t t) {
                 window_for(t);
