@@ -28,6 +28,8 @@ HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 CPP_TESTS := tests/cpp/test_HIP_impl tests/cpp/test_HIP_spec_impl tests/cpp/test_semantic_equality \
              tests/cpp/test_readers_asan tests/cpp/test_host_asan tests/cpp/test_diag_sizes_asan \
              tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4 tests/cpp/test_diag_launch
+# (built where its source is present: the engine builds against an older tests/ directory as well)
+CPP_TESTS += $(patsubst %.cpp,%,$(wildcard tests/cpp/test_chain_place.cpp))
 
 .PHONY: all lib oracle ref tests tools clean
 all: lib oracle tests tools ref
@@ -96,6 +98,14 @@ $(BUILD)/asan/test_dtab4.o: tests/cpp/test_dtab4.cpp $(HDRS) | $(BUILD)
 	mkdir -p $(BUILD)/asan
 	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -c $< -o $@
 tests/cpp/test_dtab4: $(BUILD)/asan/test_dtab4.o $(ASAN_OBJS) $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS))
+	$(HIPCC) --offload-arch=$(ARCH) $(ASAN_HOST) -o $@ $^
+
+# The chain planner on MSV-shaped models with N and C at any state index (runtime.cpp band_heavy_rows,
+# make_band_plan, make_pipe_plan) under the same sanitizers, linked as test_host_asan is; no GPU.
+$(BUILD)/asan/test_chain_place.o: tests/cpp/test_chain_place.cpp $(HDRS) | $(BUILD)
+	mkdir -p $(BUILD)/asan
+	$(HIPCC) $(HOSTFLAGS) $(ASAN_HOST) -c $< -o $@
+tests/cpp/test_chain_place: $(BUILD)/asan/test_chain_place.o $(ASAN_OBJS) $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIP_SRCS))
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN_HOST) -o $@ $^
 
 # The diagonal path variant's record sizes and offsets (kernels.h) under the same sanitizers: one

@@ -318,8 +318,39 @@ Plan make_plan(const HostModel& hm, int max_threads, bool allow_uniform) {
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// Heavy rows of the chain plan: rows with in-degree > kBandHeavy + 1, plus (repeatedly) the first light row
-// whose terms break the chain rule, while at most kBandHeavy rows are heavy.
+// Grows the heavy set until no light row breaks the chain rule: the first light row j with a term
+// from a source k that is neither heavy nor the light row before j makes j heavy, or, where that
+// leads nowhere, k (a feeder of low in-degree labelled above the light rows it feeds: N without
+// M -> N terms at a state index past M_1).  At most kBandHeavy rows are heavy, so the search visits
+// at most 2^kBandHeavy sets; a model the first choice serves at every level gets that set.
+bool grow_heavy_rows(const HostModel& hm, std::vector<uint8_t>& is_heavy, uint32_t count) {
+    const uint32_t n = hm.n;
+    uint32_t prev = 0xFFFFFFFFu, bad = 0xFFFFFFFFu, src = 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < n && bad == 0xFFFFFFFFu; ++j) {
+        if (is_heavy[j]) continue;
+        for (uint32_t e = hm.rowptr[j]; e < hm.rowptr[j + 1]; ++e) {
+            const uint32_t k = hm.col[e];
+            if (!is_heavy[k] && k != prev) {
+                bad = j;
+                src = k;
+                break;
+            }
+        }
+        prev = j;
+    }
+    if (bad == 0xFFFFFFFFu) return true;
+    if (count >= (uint32_t)kBandHeavy) return false;
+    const uint32_t cands[2] = {bad, src};
+    for (int c = 0; c < (src == bad ? 1 : 2); ++c) {  // (src == bad: a self loop, one candidate)
+        const uint32_t cand = cands[c];
+        is_heavy[cand] = 1;
+        if (grow_heavy_rows(hm, is_heavy, count + 1)) return true;
+        is_heavy[cand] = 0;
+    }
+    return false;
+}
+
+// Heavy rows of the chain plan: rows with in-degree > kBandHeavy + 1, plus the rows grow_heavy_rows adds.
 bool band_heavy_rows(const HostModel& hm, std::vector<uint32_t>* heavy_out) {
     const uint32_t n = hm.n;
     std::vector<uint8_t> is_heavy(n, 0);
@@ -329,29 +360,11 @@ bool band_heavy_rows(const HostModel& hm, std::vector<uint32_t>* heavy_out) {
             is_heavy[j] = 1;
             ++count;
         }
-    while (count <= (uint32_t)kBandHeavy) {
-        uint32_t prev = 0xFFFFFFFFu, bad = 0xFFFFFFFFu;
-        for (uint32_t j = 0; j < n && bad == 0xFFFFFFFFu; ++j) {
-            if (is_heavy[j]) continue;
-            for (uint32_t e = hm.rowptr[j]; e < hm.rowptr[j + 1]; ++e) {
-                const uint32_t k = hm.col[e];
-                if (!is_heavy[k] && k != prev) {
-                    bad = j;
-                    break;
-                }
-            }
-            prev = j;
-        }
-        if (bad == 0xFFFFFFFFu) {
-            heavy_out->clear();
-            for (uint32_t j = 0; j < n; ++j)
-                if (is_heavy[j]) heavy_out->push_back(j);
-            return true;
-        }
-        is_heavy[bad] = 1;
-        ++count;
-    }
-    return false;
+    if (count > (uint32_t)kBandHeavy || !grow_heavy_rows(hm, is_heavy, count)) return false;
+    heavy_out->clear();
+    for (uint32_t j = 0; j < n; ++j)
+        if (is_heavy[j]) heavy_out->push_back(j);
+    return true;
 }
 
 // Structure of a chain-shaped model (shared by the chain / band plans and the pipelined plan).

@@ -156,6 +156,64 @@ def random_chain_hmm(L, S=20, seed=0, self_n=True, self_c=True, feed_c=False, c_
                start_probabilities_cols=st, start_probabilities=mod(rng.uniform(0.1, 1.0, size=st.size)))
 
 
+def relabel_chain_hmm(hmm, n_at, c_at):
+    """A random_chain_hmm model (N = 0, M_1..M_L, C = L + 1) with N at state `n_at`, C at `c_at` and
+    the light rows at the remaining indices in their original order: (hmm2, new), new[old state] the
+    index map.  Only indices move: every weight, the order of the tuples and every float stay."""
+    from spec_viterbi_amd import HMM
+
+    n = int(hmm.states_num)
+    L = n - 2
+    assert 0 <= n_at < n and 0 <= c_at < n and n_at != c_at
+    new = np.empty(n, np.int64)
+    new[0], new[L + 1] = n_at, c_at
+    new[1:L + 1] = [j for j in range(n) if j not in (n_at, c_at)]
+    em = np.empty_like(hmm.emissions)
+    em[:, new] = hmm.emissions
+    hmm2 = HMM(states_num=n, emit_num=int(hmm.emit_num), trans_num=int(hmm.trans_num),
+               trans_rows=new[hmm.trans_rows.astype(np.int64)].astype(np.uint64),
+               trans_cols=new[hmm.trans_cols.astype(np.int64)].astype(np.uint64), trans_probs=hmm.trans_probs.copy(),
+               emissions=em, start_probabilities_cols=new[hmm.start_probabilities_cols.astype(np.int64)].astype(np.uint64),
+               start_probabilities=hmm.start_probabilities.copy())
+    return hmm2, new
+
+
+def chain_speculation(hmm, seq):
+    """The pipelined plans' speculation check (kernels.h, PipeModel) restated in numpy float32 for an
+    unrelabelled random_chain_hmm model (N = 0, C = L + 1; N -> C and dead light rows allowed): the
+    exact recurrence observation by observation, every add rounded on its own and associated as the
+    oracle's (emission plus weight first, then the score).  Returns (t_first, ties): the first
+    observation t >= 1 with fl(fl(E[o_t][N] + w_MN) + min_j v_{t-1}[M_j]) <
+    fl(fl(E[o_t][N] + w_NN) + v_{t-1}[N]), or -1; and the number of observations before it (all of
+    them if -1) at which the two sides are equal and finite."""
+    f32 = np.float32
+    n, S = int(hmm.states_num), int(hmm.emit_num)
+    L = n - 2
+    E = np.asarray(hmm.emissions, f32).reshape(S, n)
+    src, dst, w = hmm.trans_rows.astype(np.int64), hmm.trans_cols.astype(np.int64), np.asarray(hmm.trans_probs, f32)
+    assert np.unique(dst * n + src).size == src.size, "no duplicate transitions"
+    wmn = w[(dst == 0) & (src != 0)]
+    assert wmn.size in (0, L) and (wmn.view(np.uint32) == wmn.view(np.uint32)[:1]).all(), "M -> N: one shared weight"
+    w_mn = wmn[0] if wmn.size else f32(np.inf)
+    wnn = w[(dst == 0) & (src == 0)]
+    w_nn = wnn[0] if wnn.size else f32(np.inf)
+    start = np.full(n, np.inf, f32)
+    start[hmm.start_probabilities_cols.astype(np.int64)] = np.asarray(hmm.start_probabilities, f32)
+    v = E[int(seq[0])] + start
+    ties = 0
+    for t in range(1, len(seq)):
+        o = int(seq[t])
+        light = f32(f32(E[o][0] + w_mn) + v[1:L + 1].min())
+        own = f32(f32(E[o][0] + w_nn) + v[0])
+        if light < own:
+            return t, ties
+        ties += int(light == own and np.isfinite(own))
+        nxt = np.full(n, np.inf, f32)
+        np.minimum.at(nxt, dst, (E[o][dst] + w) + v[src])  # v'[j] = min_k fl(fl(E[o][j] + T[k][j]) + v[k])
+        v = nxt
+    return -1, ties
+
+
 def regular_hmm(n, S=4, indeg=(2,), heavy=(), heavy_terms=1.0, heavy_heavy=0, self_loops=False, zero_emis=0.0,
                 ties=False, unreachable=0, start=None, nstart=2, inf_emis=(), seed=0):
     """A random model with a controlled in-degree, so that a test can aim at one fused-kernel family.
