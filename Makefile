@@ -27,7 +27,8 @@ HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 
 CPP_TESTS := tests/cpp/test_HIP_impl tests/cpp/test_HIP_spec_impl tests/cpp/test_semantic_equality \
              tests/cpp/test_readers_asan tests/cpp/test_host_asan tests/cpp/test_diag_sizes_asan \
-             tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4 tests/cpp/test_diag_launch
+             tests/cpp/test_set_table tests/cpp/test_dispatch tests/cpp/test_dtab4 tests/cpp/test_diag_launch \
+             tests/cpp/test_set_decode_table
 # (built where its source is present: the engine builds against an older tests/ directory as well)
 CPP_TESTS += $(patsubst %.cpp,%,$(wildcard tests/cpp/test_chain_place.cpp))
 
@@ -117,6 +118,10 @@ tests/cpp/test_diag_sizes_asan: tests/cpp/test_diag_sizes_asan.cpp $(CSRC)/kerne
 tests/cpp/test_set_table: tests/cpp/test_set_table.cpp $(CSRC)/set_table.cpp $(CSRC)/set_table.h
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -I$(CSRC) \
 		-o $@ tests/cpp/test_set_table.cpp $(CSRC)/set_table.cpp
+# ... and the forward and traceback tables of a set's decode pass (members of differing row counts).
+tests/cpp/test_set_decode_table: tests/cpp/test_set_decode_table.cpp $(CSRC)/set_table.cpp $(CSRC)/set_table.h
+	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -I$(CSRC) \
+		-o $@ tests/cpp/test_set_decode_table.cpp $(CSRC)/set_table.cpp
 
 # The pass resolver (dispatch.cpp: plain host code, no HIP) under the same sanitizers.
 tests/cpp/test_dispatch: tests/cpp/test_dispatch.cpp $(CSRC)/dispatch.cpp $(CSRC)/dispatch.h include/svh.h

@@ -289,8 +289,9 @@ int svh_batch_create_u8(svh_model_t m, uint64_t nseq, const uint64_t* offsets,
  * diagonal plan, models created with another SVH_KERNEL_*) then runs its own svh_batch_run on the
  * same stream.  Results are those of the members' stand-alone runs, bit for bit.
  * Scope: scores only, levels 0 and 1 (identical).  svh_batchset_run(level >= 2) and
- * svh_batchset_create with SVH_BATCH_PATHS return SVH_E_UNSUPPORTED: decoded paths and _spec
- * level >= 2 run per batch (svh_batch_*).  Flags: SVH_BATCH_NO_TIMING only.
+ * svh_batchset_create with SVH_BATCH_PATHS return SVH_E_UNSUPPORTED: _spec level >= 2 runs per
+ * batch (svh_batch_*); decoded paths of chosen (member, row) pairs come from svh_batchset_decode
+ * (below), which needs no flag at create.  Flags: SVH_BATCH_NO_TIMING only.
  * Every model must be on one device (SVH_E_INVALID otherwise); a symbol out of range for any
  * member's alphabet is SVH_E_RANGE at create.  The models must outlive the set.
  * These entry points were appended without a change of SVH_ABI_VERSION (nothing that existed
@@ -318,6 +319,50 @@ int svh_batchset_get_info(svh_batchset_t s, svh_batchset_info* info);
 /* Milliseconds of the last svh_batchset_run: one event pair round the whole run (synchronises). */
 int svh_batchset_elapsed_ms(svh_batchset_t s, float* ms);
 int svh_batchset_destroy(svh_batchset_t s);
+
+/* ---- model sets: decoded paths of chosen (model, sequence) pairs ------------------------- */
+/* A search scores every model against every sequence (svh_batchset_run), keeps the cells whose score
+ * passes and decodes the state paths of those only.  svh_batchset_decode enqueues one decode pass for
+ * npairs pairs (member[k], row[k]) on `stream` (NULL: the first model's stream); asynchronous, like
+ * svh_batchset_run.  A pair may occur more than once: each occurrence is a row of its own.  The set
+ * builds, for every member with pairs, a path batch over that member's chosen rows (from the symbols
+ * the set was created from: nothing is uploaded by the caller); those whose own path plan is the
+ * diagonal path variant (models created with SVH_KERNEL_DIAG that it fits), whose sink row takes no
+ * term from the feeder row and whose alphabet has at most 32 symbols are GROUPED: their forward passes
+ * are one launch and their tracebacks one launch, with two nearly empty launches per grouped member for
+ * the rows whose speculation failed (the chain path variant and its traceback); every other member's
+ * decode batch runs as a stand-alone SVH_BATCH_PATHS batch does, on the same stream, after them.
+ * Results are those of stand-alone path batches, bit for bit.
+ * A decode needs no prior svh_batchset_run and reads and writes nothing of the members' scores state:
+ * svh_batch_read, svh_batch_fallbacks and svh_batch_plan on the borrowed members answer as before it,
+ * and a later svh_batchset_run is exact.  A call whose pair list equals the previous call's allocates
+ * and uploads nothing.  npairs == 0 or a null array: SVH_E_INVALID; a member or row index out of
+ * range: SVH_E_RANGE.  (Appended as the set was: SVH_ABI_VERSION is unchanged.) */
+int svh_batchset_decode(svh_batchset_t s, const uint64_t* member, const uint64_t* row, uint64_t npairs, void* stream);
+/* Pair `pair` of the last decode, in the order of its list: the row's final scores (n of that member's
+ * model), its best state, its path (the row's length) and whether the row's speculation failed and the
+ * chain path variant decoded it.  Every output pointer may be NULL.  Synchronises as svh_batch_read
+ * does and reports the decode batches' fault words (SVH_E_HIP); SVH_E_STATE before the first decode. */
+int svh_batchset_decode_read(svh_batchset_t s, uint64_t pair, float* scores, int64_t* best, int32_t* path,
+                             int32_t* fell_back, void* stream);
+typedef struct {
+    uint64_t pairs;           /* of the last decode */
+    uint64_t members;         /* members with at least one pair */
+    uint64_t grouped;         /* ... of which ran in the set's launches */
+    uint64_t grouped_pairs;   /* pairs of the grouped members */
+    uint64_t launches;        /* of the last decode: 2 + 2 x grouped (the forward set launch, the set traceback,
+                                 a chain fallback and a chain traceback per grouped member; 0 if none is
+                                 grouped) plus one per member that ran on its own */
+    uint64_t grid;            /* workgroups of the forward set launch */
+    uint64_t lds_bytes;       /* its LDS per workgroup: the largest of the grouped members' path footprints */
+    uint64_t fallback_pairs;  /* pairs whose speculation failed (synchronises) */
+    uint64_t builds;          /* decodes since create that built their batches (a repeated list builds nothing) */
+    int32_t waves;            /* sequences (waves) per workgroup of the forward set launch: 1, 2 or 4 */
+} svh_batchset_decode_info;
+int svh_batchset_decode_get_info(svh_batchset_t s, svh_batchset_decode_info* info);
+/* Milliseconds of the last decode: one event pair round the whole pass (synchronises).  SVH_E_STATE on
+ * a set created with SVH_BATCH_NO_TIMING. */
+int svh_batchset_decode_elapsed_ms(svh_batchset_t s, float* ms);
 
 /* ---- streaming ingestion (the input side of the path) ------------------ */
 /* .ess: read_emit_seq semantics (data_reader.cpp:93-134).  FASTA: fasta_to_ess.py semantics

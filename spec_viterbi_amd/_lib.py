@@ -74,6 +74,12 @@ class svh_batchset_info(ctypes.Structure):
                 ("lds_bytes", c_uint64), ("waves", c_int32)]
 
 
+class svh_batchset_decode_info(ctypes.Structure):
+    _fields_ = [("pairs", c_uint64), ("members", c_uint64), ("grouped", c_uint64), ("grouped_pairs", c_uint64),
+                ("launches", c_uint64), ("grid", c_uint64), ("lds_bytes", c_uint64), ("fallback_pairs", c_uint64),
+                ("builds", c_uint64), ("waves", c_int32)]
+
+
 P_u64 = POINTER(c_uint64)
 P_f32 = POINTER(c_float)
 P_i64 = POINTER(c_int64)
@@ -125,6 +131,10 @@ SIGNATURES = {
     "svh_batchset_get_info": (c_int, [c_void_p, POINTER(svh_batchset_info)]),
     "svh_batchset_elapsed_ms": (c_int, [c_void_p, P_f32]),
     "svh_batchset_destroy": (c_int, [c_void_p]),
+    "svh_batchset_decode": (c_int, [c_void_p, P_u64, P_u64, c_uint64, c_void_p]),
+    "svh_batchset_decode_read": (c_int, [c_void_p, c_uint64, P_f32, P_i64, P_i32, P_i32, c_void_p]),
+    "svh_batchset_decode_get_info": (c_int, [c_void_p, POINTER(svh_batchset_decode_info)]),
+    "svh_batchset_decode_elapsed_ms": (c_int, [c_void_p, P_f32]),
     "svh_reader_open": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
     "svh_reader_next": (c_int, [c_void_p, c_uint64, c_uint64, P_u64, POINTER(P_u64),
                                 POINTER(POINTER(ctypes.c_uint8))]),

@@ -19,6 +19,23 @@ __device__ __forceinline__ void lds_barrier() {
 
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
+// A pointer read from a descriptor table in device memory (the model sets' kernels: diag.hip,
+// pipe_paths.hip) is device memory.  The compiler knows that of a kernel's own pointer arguments and
+// not of a pointer it loaded: said so here (the global pointer goes through an empty asm statement, so
+// that the cast pair is not folded away), the accesses through it are global loads and stores from
+// scalar bases, not flat ones, which count against LDS waits as well.  (The descriptor is
+// wave-uniform: "s".)
+template <class T>
+__device__ __forceinline__ void in_global1(T*& p) {
+    auto g = (__attribute__((address_space(1))) T*)p;
+    asm volatile("" : "+s"(g));
+    p = (T*)g;
+}
+template <class... T>
+__device__ __forceinline__ void in_global(T*&... p) {
+    (in_global1(p), ...);
+}
+
 // Wave-wide minimum, valid in lane 63.  Six DPP stages fused into v_min_f32_dpp (quad swaps,
 // half-row / row mirrors, row broadcasts 15 and 31); rows masked off by row_mask keep their value,
 // which is the identity for min.  s_nop 1 covers the VALU-write -> DPP-read hazard.

@@ -223,48 +223,33 @@ void diag_viterbi_kernel(PipeModel m, FusedBatch b, PipeScratch x) {
 // m, b and x everywhere (partials, arrival counts, the re-run).  Workgroups of different entries share
 // nothing: no wait, no spin, no communication is added.
 //
-// A pointer read from the descriptor table is device memory.  The compiler knows that of a kernel's
-// own pointer arguments and not of a pointer it loaded: said so here (the global pointer goes through
-// an empty asm statement, so that the cast pair is not folded away), the body's accesses are global
-// loads and stores from scalar bases as in the plain kernel, not flat ones, which count against the
-// steps' LDS waits as well.  (The descriptor is wave-uniform: "s".)
-template <class T>
-__device__ __forceinline__ void in_global1(T*& p) {
-    auto g = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+s"(g));
-    p = (T*)g;
-}
-template <class... T>
-__device__ __forceinline__ void in_global(T*&... p) {
-    (in_global1(p), ...);
-}
+// A pointer read from the descriptor table is device memory: every one the body uses goes through
+// in_global (device_common.h), so that its accesses are global loads and stores from scalar bases as in
+// the plain kernel, not flat ones, which count against the steps' LDS waits as well.
+// The lookup and the descriptor are diag_set_entry.h, text shared with the path variant below.
 template <int W>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
 void diag_set_kernel(const DiagSetEntry* __restrict__ e, const uint32_t* __restrict__ first, uint32_t ne) {
     constexpr bool SX = false, PATHS = false, LD = false, FL = false, QD = false;
     constexpr int DM = 1;
-    const uint32_t lane = threadIdx.x & 63u, gbx = blockIdx.x;
-    uint32_t cnt = 0;
-    for (uint32_t i0 = 0; i0 < ne; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        const bool le = i < ne && first[i] <= gbx;
-        const uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
-        cnt += c;
-        if (c < 64) break;
+#include "diag_set_entry.h"
+    {
+#include "diag_body.h"
     }
-    if (cnt == 0) return;  // (first[0] = 0: every block has an entry)
-    const uint32_t i = (uint32_t)uniform((int)(cnt - 1));
-    const uint32_t f0 = first[i];
-    DiagSetEntry ent = e[i];
-    in_global(ent.m.tab, ent.m.e0, ent.m.start, ent.m.lrow, ent.m.hc, ent.m.dtab, ent.m.pflags, ent.m.spos, ent.m.stamps, ent.m.dtab2,
-              ent.m.dtab4);
-    in_global(ent.b.symbols, ent.b.sym_off, ent.b.begin, ent.b.end, ent.b.v_in, ent.b.v_in_row, ent.b.scores, ent.b.best,
-              ent.b.run_mask, ent.b.fault);
-    in_global(ent.x.ctr, ent.x.done, ent.x.part, ent.x.gran, ent.x.cons, ent.x.viol, ent.x.xcc);
-    const PipeModel& m = ent.m;
-    const FusedBatch& b = ent.b;
-    const PipeScratch& x = ent.x;
-    const uint32_t bx = gbx - f0;
+}
+
+// The decode pass of a set (BatchSet::decode): the same lookup, the body's path variant.  The entries'
+// batches -- each member's chosen rows -- differ in their sequence counts; entry i's grid is its own
+// launch's at this W (an entry with fewer rows than W has idle waves, as the last group of a
+// stand-alone launch has).  The record pointers and their offset tables go through in_global with the
+// others.  Rows whose speculation fails are flagged in the entry's own x.viol and left to the host's
+// chain launch for that entry; nothing is re-run here.
+template <int W>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2)))
+void diag_set_paths_kernel(const DiagSetEntry* __restrict__ e, const uint32_t* __restrict__ first, uint32_t ne) {
+    constexpr bool SX = false, PATHS = true, LD = false, FL = false, QD = false;
+    constexpr int DM = 1;
+#include "diag_set_entry.h"
     {
 #include "diag_body.h"
     }
@@ -358,22 +343,29 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
     return launch_fn(fn, L.grid, L.threads, L.lds_request, args, stream);
 }
 
-hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out) {
+hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out, bool paths) {
     if (!host || !first_host || !out || ne == 0 || first_host[0] != 0 || !kVariants) return hipErrorInvalidValue;
-    const uint32_t nseq = host[0].b.nseq;
+    // one W per launch: the scores entries share their sequence count; a decode's entries take what the
+    // largest of them would get on its own
+    uint32_t nseq = host[0].b.nseq;
+    if (paths)
+        for (uint32_t i = 1; i < ne; ++i) nseq = std::max(nseq, host[i].b.nseq);
     if (nseq == 0) return hipErrorInvalidValue;
-    const uint32_t W = diag_resolve(diag_caps(host[0].m), {nseq}).W;
+    const uint32_t W = diag_resolve(diag_caps(host[0].m), {nseq, false, paths}).W;
     size_t lds = 0;
     for (uint32_t i = 0; i < ne; ++i) {
         const PipeModel& m = host[i].m;
         const FusedBatch& b = host[i].b;
-        // a scores view launch_diag takes, and the set's own conditions: no X_SF term, one W, every input
-        if (!diag_view_ok(m, b, host[i].x) || !diag_set_model_ok(m) || b.cmask || b.nseq != nseq || !b.symbols || !b.sym_off ||
-            !b.begin || !b.end || !b.scores)
+        // a view launch_diag takes (scores: b.cmask null; paths: with every record buffer), and the
+        // set's own conditions: no X_SF term, one W, every input
+        if (!diag_view_ok(m, b, host[i].x) || !diag_set_model_ok(m) || (b.cmask != nullptr) != paths || b.nseq == 0 ||
+            (!paths && b.nseq != nseq) || !b.symbols || !b.sym_off || !b.begin || !b.end || !b.scores)
             return hipErrorInvalidValue;
-        const uint64_t blocks = ((uint64_t)nseq + W - 1) / W * m.nrng;
+        if (paths && (!diag_paths_fit(m.S, false) || !m.ties_heavy)) return hipErrorInvalidValue;
+        const uint64_t blocks = ((uint64_t)b.nseq + W - 1) / W * m.nrng;
         if (first_host[i + 1] < first_host[i] || (uint64_t)first_host[i + 1] - first_host[i] != blocks) return hipErrorInvalidValue;
-        lds = std::max(lds, diag_lds_scores(kDK, W, m.S, m.P, false, 1, false, false));  // (the plain variant, one diagonal per lane)
+        // (the plain variant, one diagonal per lane)
+        lds = std::max(lds, paths ? diag_lds_paths(kDK, W, m.S, false) : diag_lds_scores(kDK, W, m.S, m.P, false, 1, false, false));
     }
     if (first_host[ne] > 0x7FFFFFFFu || lds > kDiagLdsMax) return hipErrorInvalidValue;
     out->grid = first_host[ne];
@@ -382,15 +374,19 @@ hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, u
     return hipSuccess;
 }
 
+template <int W>
+const void* set_kernel_fn(bool paths) {
+    static_assert(kDK == 64, "the path records' block layout (diag_kernel_w)");
+    return paths ? reinterpret_cast<const void*>(&diag_set_paths_kernel<W>) : reinterpret_cast<const void*>(&diag_set_kernel<W>);
+}
+
 hipError_t launch_diag_set(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, const DiagSetEntry* entries,
-                           const uint32_t* first, uint32_t cus, hipStream_t stream) {
+                           const uint32_t* first, uint32_t cus, hipStream_t stream, bool paths) {
     DiagSetLaunch L{};
-    const hipError_t pe = diag_set_plan(host, first_host, ne, &L);
+    const hipError_t pe = diag_set_plan(host, first_host, ne, &L, paths);
     if (pe != hipSuccess) return pe;
     if (!entries || !first) return hipErrorInvalidValue;
-    const void* fn = L.waves == 4   ? reinterpret_cast<const void*>(&diag_set_kernel<4>)
-                     : L.waves == 2 ? reinterpret_cast<const void*>(&diag_set_kernel<2>)
-                                    : reinterpret_cast<const void*>(&diag_set_kernel<1>);
+    const void* fn = L.waves == 4 ? set_kernel_fn<4>(paths) : L.waves == 2 ? set_kernel_fn<2>(paths) : set_kernel_fn<1>(paths);
     const DiagSetEntry* ea = entries;
     const uint32_t* fa = first;
     uint32_t na = ne;

@@ -344,9 +344,9 @@ hipError_t launch_diag(const PipeModel& m, const FusedBatch& b, const PipeScratc
 // (model, batch, scratch) triples.  A table of DiagSetEntry in device memory and a prefix table
 // first[ne + 1] of the entries' first blocks (set_table.h; first[ne] = the grid); a workgroup finds the
 // last entry i with first[i] <= blockIdx.x and runs the plan's body as block blockIdx.x - first[i] of
-// that entry's own launch.  Scores only, models without an X_SF term and with at most 32 symbols, one
-// diagonal per lane, no loader wave; every entry's batch has the same number of sequences (one W per
-// launch).  host[] is the host copy of the table at entries (validated as launch_diag validates its
+// that entry's own launch.  Models without an X_SF term and with at most 32 symbols, one diagonal per
+// lane, no loader wave; scores: every entry's batch has the same number of sequences (one W per
+// launch); the path variant is the decode pass below.  host[] is the host copy of the table at entries (validated as launch_diag validates its
 // arguments; its largest LDS footprint is the launch's); cus: the device's CUs (even placement, 0: off).
 struct DiagSetEntry {
     PipeModel m;
@@ -359,9 +359,28 @@ struct DiagSetLaunch {
     uint32_t waves;
 };
 // what launch_diag_set would launch for this table (hipErrorInvalidValue: an entry it does not take)
-hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out);
+// paths: the decode pass of a set (BatchSet::decode), diag_set_paths_kernel -- every entry a view
+// launch_diag takes as a paths view (b.cmask and every record buffer); the entries' batches may differ
+// in their sequence counts (entry i has ceil(b.nseq / W) x nrng blocks, W what diag_resolve gives a
+// paths query for the largest of them); the LDS is the largest diag_lds_paths of the entries.  Rows
+// whose speculation fails are flagged in the entry's own x.viol, as by launch_diag.
+hipError_t diag_set_plan(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, DiagSetLaunch* out,
+                         bool paths = false);
 hipError_t launch_diag_set(const DiagSetEntry* host, const uint32_t* first_host, uint32_t ne, const DiagSetEntry* entries,
-                           const uint32_t* first, uint32_t cus, hipStream_t stream);
+                           const uint32_t* first, uint32_t cus, hipStream_t stream, bool paths = false);
+// The traceback of a set's decode pass (pipe_paths.hip diag_set_traceback_kernel): one launch of
+// launch_diag_traceback's walk over the rows of many (model, batch) pairs, one wave per row.  tfirst is
+// the prefix table of the entries' row counts (set_table.h build_set_row_table): block bx serves row
+// bx - tfirst[i] of the last entry i with tfirst[i] <= bx, found as diag_set_kernel finds its entry.
+struct DiagSetTbEntry {
+    PipeModel m;
+    FusedBatch b;
+    const uint64_t* path_off;
+    int32_t* paths;
+    const uint32_t* skip;  // rows flagged by the forward launch (x.viol): left to the chain traceback
+};
+hipError_t launch_diag_set_traceback(const DiagSetTbEntry* host, const uint32_t* tfirst_host, uint32_t ne,
+                                     const DiagSetTbEntry* entries, const uint32_t* tfirst, hipStream_t stream);
 // _spec level 2 on the diagonal plan (diag_l2.hip): every chunk of two observations of every row in
 // one launch -- a lane advances two positions per chunk, so its chain input is again its own score.
 // Row q starts from the first observation's state in b.v_in (row q) and ends in b.scores (row q;

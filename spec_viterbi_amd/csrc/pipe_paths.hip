@@ -208,9 +208,11 @@ __device__ uint32_t pipe_jstar(const PipeModel& m, const Src& rs, const float* c
 // no loads; S (and F otherwise) rebuild their inputs on demand (RecSrc).
 // DIAG: the diagonal plan's records (DiagSrc): the light run reads one diagonal's words, S's scores
 // of a round come from diag_c_window, j* from the plan's own checkpoint rows.
+// The walk of row q is a function of the launch's arguments and q: pipe_traceback_kernel runs it for
+// blockIdx.x, the model sets' diag_set_traceback_kernel for the row of the entry it looked up.
 template <bool DIAG>
-__global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBatch b, const uint64_t* path_off,
-                                                             int32_t* paths, const uint32_t* skip) {
+__device__ __forceinline__ void pipe_traceback_row(const PipeModel& m, const FusedBatch& b, const uint64_t* path_off,
+                                                   int32_t* paths, const uint32_t* skip, const uint32_t q) {
     __shared__ float buf[2 * kPTbMaxP];
     // the walk's per-round lookups, staged in LDS (the masks, partials and symbols of a round's
     // 64 observations are its only global loads)
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
     __shared__ int32_t sposl[kPTbMaxN];
     __shared__ uint32_t lrowl[kPTbMaxP];
     __shared__ uint8_t pfl[kPTbMaxP];
-    const uint32_t q = blockIdx.x, lane = threadIdx.x;
+    const uint32_t lane = threadIdx.x;
     if (skip && skip[q]) return;  // re-run (and traced) by the chain kernel
     for (uint32_t x = lane; x < m.S * 8; x += 64) hcl[x] = m.hc[x];
     for (uint32_t x = lane; x < m.n; x += 64) sposl[x] = m.spos[x];
@@ -347,6 +349,39 @@ __global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBa
     }
 }
 
+template <bool DIAG>
+__global__ __launch_bounds__(64) void pipe_traceback_kernel(PipeModel m, FusedBatch b, const uint64_t* path_off,
+                                                             int32_t* paths, const uint32_t* skip) {
+    pipe_traceback_row<DIAG>(m, b, path_off, paths, skip, blockIdx.x);
+}
+
+// Model sets, the decode pass (kernels.h DiagSetTbEntry): block bx walks row bx - tfirst[i] of the last
+// entry i with tfirst[i] <= bx -- diag_set_kernel's lookup (diag_set_entry.h) over a table with one
+// block per row -- with that entry's model, records, paths and flags.  The descriptor's pointers are
+// device memory (in_global, device_common.h).  One wave per block; blocks share nothing.
+__global__ __launch_bounds__(64) void diag_set_traceback_kernel(const DiagSetTbEntry* __restrict__ e,
+                                                                 const uint32_t* __restrict__ tfirst, uint32_t ne) {
+    const uint32_t lane = threadIdx.x & 63u, gbx = blockIdx.x;
+    uint32_t cnt = 0;
+    for (uint32_t i0 = 0; i0 < ne; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        const bool le = i < ne && tfirst[i] <= gbx;
+        const uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
+        cnt += c;
+        if (c < 64) break;
+    }
+    if (cnt == 0) return;  // (tfirst[0] = 0: every block has an entry)
+    const uint32_t i = (uint32_t)uniform((int)(cnt - 1));
+    const uint32_t q = gbx - tfirst[i];
+    DiagSetTbEntry ent = e[i];
+    if (q >= ent.b.nseq) return;  // (the table is built from the entries' row counts: never)
+    in_global(ent.m.tab, ent.m.hc, ent.m.lrow, ent.m.pflags, ent.m.spos);
+    in_global(ent.b.symbols, ent.b.sym_off, ent.b.end, ent.b.best, ent.b.cmask, ent.b.cmask_off, ent.b.ckpt, ent.b.ckpt_off,
+              ent.b.prec, ent.b.prec_off, ent.b.fck, ent.b.fck_off, ent.b.hrec, ent.b.hrec_off);
+    in_global(ent.path_off, ent.paths, ent.skip);
+    pipe_traceback_row<true>(ent.m, ent.b, ent.path_off, ent.paths, ent.skip, q);
+}
+
 }  // namespace
 
 hipError_t launch_pipe_traceback(const PipeModel& m, const FusedBatch& b, const uint64_t* path_off, int32_t* paths,
@@ -366,6 +401,25 @@ hipError_t launch_diag_traceback(const PipeModel& m, const FusedBatch& b, const 
         return hipErrorInvalidValue;
     if (b.nseq == 0) return hipSuccess;
     hipLaunchKernelGGL(pipe_traceback_kernel<true>, dim3(b.nseq), dim3(64), 0, stream, m, b, path_off, paths, skip);
+    return hipGetLastError();
+}
+
+hipError_t launch_diag_set_traceback(const DiagSetTbEntry* host, const uint32_t* tfirst_host, uint32_t ne,
+                                     const DiagSetTbEntry* entries, const uint32_t* tfirst, hipStream_t stream) {
+    if (!host || !tfirst_host || !entries || !tfirst || ne == 0 || tfirst_host[0] != 0) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < ne; ++i) {  // launch_diag_traceback's conditions, entry by entry
+        const PipeModel& m = host[i].m;
+        const FusedBatch& b = host[i].b;
+        if (!b.cmask || !b.ckpt || !b.prec || !b.fck || !b.hrec || !m.tab || m.wide || !m.nrng || !m.ties_heavy || m.sx ||
+            !m.pflags || !m.spos || m.P > kPTbMaxP || (size_t)m.nrng * 64 > m.P || m.n > kPTbMaxN || m.S > 32)
+            return hipErrorInvalidValue;
+        if (!b.cmask_off || !b.ckpt_off || !b.prec_off || !b.fck_off || !b.hrec_off || !b.symbols || !b.sym_off || !b.end ||
+            !b.best || !host[i].path_off || !host[i].paths || b.nseq == 0)
+            return hipErrorInvalidValue;
+        if (tfirst_host[i + 1] < tfirst_host[i] || tfirst_host[i + 1] - tfirst_host[i] != b.nseq) return hipErrorInvalidValue;
+    }
+    if (tfirst_host[ne] > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(diag_set_traceback_kernel, dim3(tfirst_host[ne]), dim3(64), 0, stream, entries, tfirst, ne);
     return hipGetLastError();
 }
 

@@ -1878,6 +1878,41 @@ FusedBatch Batch::scores_view() const {
     return fb;
 }
 
+FusedBatch Batch::records_view() const {
+    FusedBatch fb = scores_view();
+    if (paths && chain_paths) {
+        fb.cmask = d_cmask.as<uint32_t>();
+        fb.cmask_off = p_cmoff;
+        fb.hrec = d_hrec.as<uint32_t>();
+        fb.hrec_off = p_hroff;
+        fb.ckpt = d_ckpt.as<float>();
+        fb.ckpt_off = p_ckoff;
+    } else if (paths) {
+        fb.bp = d_bp.as<uint16_t>();
+        fb.bp_off = p_bpoff;
+    }
+    return fb;
+}
+
+void Batch::path_plan_views(const FusedBatch& fb, FusedBatch* pb, FusedBatch* cb) const {
+    *cb = fb;  // chain buffers
+    cb->run_mask = pipe.view.viol;
+    cb->pipe = nullptr;
+    *pb = fb;
+    pb->cmask = d_pmask.as<uint32_t>();
+    pb->cmask_off = p_pmoff;
+    pb->ckpt = d_pck.as<float>();
+    pb->ckpt_off = p_pcoff;
+    pb->prec = d_prec.as<float2>();  // (diagonal: floats [nrng][len] per sequence, offsets in floats)
+    pb->prec_off = p_proff;
+    pb->fck = d_fck.as<float>();
+    pb->fck_off = p_fcoff;
+    if (diag_paths) {
+        pb->hrec = d_dcc.as<uint32_t>();  // floats [nrng][checkpoints] per sequence
+        pb->hrec_off = p_dcoff;
+    }
+}
+
 const DevicePipePlan* Batch::set_plan() const {
     if (paths || plan.step != StepKernel::Diag) return nullptr;
     const DevicePipePlan* dp = &model->pipe_plan(plan);
@@ -1899,6 +1934,51 @@ void Batch::begin_set_run(hipStream_t s, DiagSetEntry* e) {
     e->x = pipe.view;
 }
 
+const DevicePipePlan* Batch::set_decode_plan() const {
+    if (!paths || !diag_paths) return nullptr;
+    const DevicePipePlan* dp = &model->pipe_plan(plan);
+    return diag_set_model_ok(dp->view) ? dp : nullptr;
+}
+
+void Batch::begin_set_decode(hipStream_t s, DiagSetEntry* e, DiagSetTbEntry* t) {
+    std::lock_guard<std::mutex> lock(model->mu);
+    DeviceGuard g(model->device);
+    const DevicePipePlan* dp = set_decode_plan();
+    if (!dp || !e || !t) throw Error(SVH_E_STATE, "batch set: decode batch is not planned on the diagonal path variant");
+    pipe.ensure(nseq, plan.scratch_G, s);
+    pipe_ran = true;
+    l2_ran = false;
+    last_stream = s;
+    ran = true;
+    FusedBatch pb, cb;
+    path_plan_views(records_view(), &pb, &cb);  // (FusedBatch::pipe stays null: a host-side field)
+    e->m = dp->view;
+    e->b = pb;
+    e->x = pipe.view;
+    t->m = dp->view;
+    t->b = pb;
+    t->path_off = p_pathoff;
+    t->paths = d_paths.as<int32_t>();
+    t->skip = pipe.view.viol;
+}
+
+void Batch::set_decode_chain(hipStream_t s) {
+    std::lock_guard<std::mutex> lock(model->mu);
+    DeviceGuard g(model->device);
+    FusedBatch pb, cb;
+    path_plan_views(records_view(), &pb, &cb);
+    hip_check(launch_chain(model->band.view, 1, cb, s), "chain Viterbi kernel (set decode fallback)");
+}
+
+void Batch::set_decode_chain_traceback(hipStream_t s) {
+    std::lock_guard<std::mutex> lock(model->mu);
+    DeviceGuard g(model->device);
+    FusedBatch pb, cb;
+    path_plan_views(records_view(), &pb, &cb);
+    hip_check(launch_chain_traceback(model->band.view, cb, p_pathoff, d_paths.as<int32_t>(), s),
+              "chain traceback kernel (set decode fallback)");
+}
+
 void Batch::run(uint32_t level, hipStream_t s) {
     std::lock_guard<std::mutex> lock(model->mu);
     DeviceGuard g(model->device);
@@ -1909,18 +1989,7 @@ void Batch::run(uint32_t level, hipStream_t s) {
         throw Error(SVH_E_STATE, "run at _spec level " + std::to_string(level) +
                                      " needs svh_spec_build(" + std::to_string(level) + ") first");
     const CsrModel csr = model->csr_view();
-    FusedBatch fb = scores_view();
-    if (paths && chain_paths) {
-        fb.cmask = d_cmask.as<uint32_t>();
-        fb.cmask_off = p_cmoff;
-        fb.hrec = d_hrec.as<uint32_t>();
-        fb.hrec_off = p_hroff;
-        fb.ckpt = d_ckpt.as<float>();
-        fb.ckpt_off = p_ckoff;
-    } else if (paths) {
-        fb.bp = d_bp.as<uint16_t>();
-        fb.bp_off = p_bpoff;
-    }
+    FusedBatch fb = records_view();
     l2_ran = false;
     // level <= 1: the plan of the load; level >= 2: the chunk route and the tail's plan as the model's
     // _spec state stands now (spec_build may have run since the load)
@@ -1940,22 +2009,8 @@ void Batch::run(uint32_t level, hipStream_t s) {
         // chain traceback (flagged rows)
         const DevicePipePlan& ppl = model->pipe_plan(pl);
         const DeviceBandPlan& bpl = model->band;
-        FusedBatch cb = fb;  // chain buffers
-        cb.run_mask = pipe.view.viol;
-        cb.pipe = nullptr;
-        FusedBatch pb = fb;
-        pb.cmask = d_pmask.as<uint32_t>();
-        pb.cmask_off = p_pmoff;
-        pb.ckpt = d_pck.as<float>();
-        pb.ckpt_off = p_pcoff;
-        pb.prec = d_prec.as<float2>();  // (diagonal: floats [nrng][len] per sequence, offsets in floats)
-        pb.prec_off = p_proff;
-        pb.fck = d_fck.as<float>();
-        pb.fck_off = p_fcoff;
-        if (diag_paths) {
-            pb.hrec = d_dcc.as<uint32_t>();  // floats [nrng][checkpoints] per sequence
-            pb.hrec_off = p_dcoff;
-        }
+        FusedBatch cb, pb;
+        path_plan_views(fb, &pb, &cb);
         hip_check(diag_paths       ? launch_diag(ppl.view, pb, pipe.view, s)
                   : ppl.plan.wide ? launch_pipew(ppl.view, pb, pipe.view, s)
                                   : launch_pipe(ppl.view, pb, pipe.view, s),

@@ -370,11 +370,25 @@ struct Batch {
     // the diagonal plan of this batch's scores pass if a set launch can take it (nullptr: the
     // member runs on its own): no X_SF term, at most kDiagMaxSym symbols
     const DevicePipePlan* set_plan() const;
+    // BatchSet::decode, for a path batch over a member's chosen rows.  set_decode_plan: the diagonal
+    // plan of its path pass if the set's launches can take it (as set_plan; nullptr: its own run()).
+    // begin_set_decode: what run() does for a path batch on the diagonal plan before launch_diag,
+    // without the launch; *e / *t = the forward and the traceback launch's descriptors of this batch.
+    // set_decode_chain / _chain_traceback: the pass's second and fourth launch (the chain path variant
+    // over the rows the forward launch flagged, and their traceback), as run() launches them.
+    const DevicePipePlan* set_decode_plan() const;
+    void begin_set_decode(hipStream_t s, DiagSetEntry* e, DiagSetTbEntry* t);
+    void set_decode_chain(hipStream_t s);
+    void set_decode_chain_traceback(hipStream_t s);
 
   private:
     void init(uint32_t flags);
     void report_fault(uint32_t f, hipStream_t s);
     FusedBatch scores_view() const;  // the inputs and the result arena as the step kernels take them
+    FusedBatch records_view() const;  // ... with the chain kernel's path records or the backpointers (paths)
+    // a path pass on the pipelined or the diagonal plan, from records_view(): *pb the plan's own record
+    // buffers (its path variant, its traceback), *cb the chain fallback's view (flagged rows only)
+    void path_plan_views(const FusedBatch& fb, FusedBatch* pb, FusedBatch* cb) const;
 };
 
 // Model sets: one batch of sequences scored against many models.  The set owns one Batch per model,
@@ -382,7 +396,8 @@ struct Batch {
 // batch (read, pipe_fallbacks, the plan, the fault report) works on a member unchanged.  run()
 // launches every grouped member -- one whose own scores plan is the diagonal plan, without an X_SF
 // term, of at most kDiagMaxSym symbols -- in ONE launch of diag_set_kernel, then every other
-// member's own Batch::run on the same stream.  Levels 0 and 1, scores only.
+// member's own Batch::run on the same stream.  Levels 0 and 1, scores only; decode() gives the state
+// paths of chosen (member, row) pairs in the same manner, from path batches of its own.
 struct BatchSet {
     std::mutex mu;  // run() / info() / elapsed_ms() of one set are serialised
     std::vector<std::unique_ptr<Batch>> members;
@@ -405,9 +420,54 @@ struct BatchSet {
     svh_batchset_info info();
     float elapsed_ms();
 
+    // Decoded paths of chosen (member, row) pairs (svh_batchset_decode).  A decode builds, for every
+    // member with pairs, a path batch over that member's chosen rows, in the order of the list (a pair
+    // listed twice is two rows) -- its own symbols copy, record buffers, result arena, fault word and
+    // scratch: the members' scores state is not touched.  A decode batch whose own path plan is the
+    // diagonal path variant (set_decode_plan) is grouped: the grouped batches' forward passes are ONE
+    // launch of the set kernel's path variant and their tracebacks ONE launch of the set traceback, with
+    // each batch's chain fallback and chain traceback launched between and after them as its own run()
+    // launches them; every other decode batch runs its own run(), on the same stream, after those.
+    // A call whose list equals the previous call's builds and uploads nothing.
+    void decode(const uint64_t* member, const uint64_t* row, uint64_t npairs, hipStream_t s);
+    // pair `pair` of the last decode (synchronises; the first read after a decode fetches every decode
+    // batch's results and reports their fault words); every pointer may be null
+    void decode_read(uint64_t pair, float* scores, int64_t* best, int32_t* path, int32_t* fell_back, hipStream_t s);
+    svh_batchset_decode_info decode_info();
+    float decode_elapsed_ms();
+
   private:
     // every grouped member's begin_set_run; the table is uploaded (on s) when a descriptor changed
     void refresh(hipStream_t s);
+
+    std::vector<uint64_t> h_offsets;  // the sequences the set was created from
+    std::vector<uint8_t> h_symbols;
+    struct Decode {
+        std::vector<uint64_t> member, row;             // the list of the last decode
+        std::vector<std::unique_ptr<Batch>> batch;     // [members] (kept, and reloaded, from decode to decode)
+        std::vector<uint32_t> rows;                    // [members] chosen rows (0: no part in the decode)
+        std::vector<uint8_t> grouped;                  // [members]
+        std::vector<uint32_t> pair_row;                // [pairs] the pair's row in its member's decode batch
+        SetTable table, ttable;                        // forward blocks / one block per row
+        std::vector<DiagSetEntry> h_entries;
+        std::vector<DiagSetTbEntry> h_tentries;
+        DeviceBuffer d_entries, d_tentries, d_first, d_tfirst;
+        DiagSetLaunch launch{};
+        uint64_t grouped_pairs = 0, launches = 0, builds = 0;
+        hipStream_t stream = nullptr;                  // of the last decode
+        bool ran = false;
+        // host copy of the last decode's results, fetched by the first decode_read / decode_info after it
+        bool fetched = false;
+        std::vector<std::vector<float>> scores;
+        std::vector<std::vector<int64_t>> best;
+        std::vector<std::vector<int32_t>> paths;
+        std::vector<std::vector<uint32_t>> fell;
+        uint64_t fallback_pairs = 0;
+    } dec;
+    hipEvent_t dec_start = nullptr, dec_stop = nullptr;
+    void decode_build(const uint64_t* member, const uint64_t* row, uint64_t npairs);
+    void decode_refresh(hipStream_t s);  // (as refresh, for both descriptor tables)
+    void decode_fetch(hipStream_t s);
 };
 
 }  // namespace svh

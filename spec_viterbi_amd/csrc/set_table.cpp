@@ -30,6 +30,17 @@ bool build_set_table(const SetMember* members, uint64_t count, SetTable* out, st
     return true;
 }
 
+bool build_set_row_table(const SetMember* members, uint64_t count, SetTable* out, std::string* err) {
+    if (count && !members) {
+        if (err) *err = "null argument";
+        return false;
+    }
+    std::vector<SetMember> rows(members, members + count);
+    for (SetMember& m : rows)
+        if (m.grouped) m.nrng = 1, m.waves = 1;  // a block per sequence
+    return build_set_table(rows.data(), count, out, err);
+}
+
 void set_table_lookup(const SetTable& t, uint32_t bx, uint32_t* entry, uint32_t* local) {
     const uint32_t ne = t.entries();
     uint32_t cnt = 0;

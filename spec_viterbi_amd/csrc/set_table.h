@@ -31,6 +31,11 @@ constexpr uint64_t kSetMaxGrid = 0x7FFFFFFFull;
 // skipped whatever they hold.  No grouped member: an empty table, grid 0.
 bool build_set_table(const SetMember* members, uint64_t count, SetTable* out, std::string* err = nullptr);
 
+// The table of a launch with one block per sequence of the same members (the set traceback,
+// pipe_paths.hip): entry e is the same member as in build_set_table's table and covers nseq blocks,
+// whatever the member's ranges and workgroup width.  Refused as there.
+bool build_set_row_table(const SetMember* members, uint64_t count, SetTable* out, std::string* err = nullptr);
+
 // The entry of block bx (the last e with first[e] <= bx) and the block's index within it: what the
 // kernel's lookup computes, in its chunks of 64.  bx < grid.
 void set_table_lookup(const SetTable& t, uint32_t bx, uint32_t* entry, uint32_t* local);

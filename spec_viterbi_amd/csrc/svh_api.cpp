@@ -402,6 +402,35 @@ int svh_batchset_destroy(svh_batchset_t s) {
     return guarded([&] { delete s; });
 }
 
+int svh_batchset_decode(svh_batchset_t s, const uint64_t* member, const uint64_t* row, uint64_t npairs, void* stream) {
+    return guarded([&] {
+        require(s != nullptr, "null batch set");
+        s->impl->decode(member, row, npairs, static_cast<hipStream_t>(stream));
+    });
+}
+
+int svh_batchset_decode_read(svh_batchset_t s, uint64_t pair, float* scores, int64_t* best, int32_t* path, int32_t* fell_back,
+                             void* stream) {
+    return guarded([&] {
+        require(s != nullptr, "null batch set");
+        s->impl->decode_read(pair, scores, best, path, fell_back, static_cast<hipStream_t>(stream));
+    });
+}
+
+int svh_batchset_decode_get_info(svh_batchset_t s, svh_batchset_decode_info* info) {
+    return guarded([&] {
+        require(s && info, "null argument");
+        *info = s->impl->decode_info();
+    });
+}
+
+int svh_batchset_decode_elapsed_ms(svh_batchset_t s, float* ms) {
+    return guarded([&] {
+        require(s && ms, "null argument");
+        *ms = s->impl->decode_elapsed_ms();
+    });
+}
+
 namespace {
 // svh_viterbi*: the model's kept batch (scores only / with paths), reloaded from the caller's
 // symbols in whichever form they come, then one run and one read (throws; callers guard)

@@ -328,6 +328,46 @@ class DeviceBatchSet:
         _lib.check(_lib.lib.svh_batchset_elapsed_ms(self._h, ctypes.byref(ms)))
         return float(ms.value)
 
+    def decode(self, pairs, stream: int | None = None) -> None:
+        """Enqueue one decode pass for `pairs`, a sequence of (member, row) (svh_batchset_decode): the
+        state paths of those cells only.  A pair listed twice is decoded twice; the members' scores
+        state is untouched; the same list again builds and uploads nothing."""
+        pr = np.ascontiguousarray(np.asarray(list(pairs), np.uint64).reshape(-1, 2))
+        mem, row = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        _lib.check(_lib.lib.svh_batchset_decode(self._h, _p(mem, _u64) if mem.size else None,
+                                                _p(row, _u64) if row.size else None, int(mem.size),
+                                                ctypes.c_void_p(stream or 0)))
+        self._decoded = [(int(m), int(r)) for m, r in zip(mem, row)]
+
+    def read_decoded(self, stream: int | None = None, fell_back: bool = False) -> list:
+        """[(scores [n_member], best, path [row length])] of the last decode, in pair order
+        (svh_batchset_decode_read); fell_back=True appends to each tuple whether the chain path variant
+        decoded the row."""
+        if getattr(self, "_decoded", None) is None:  # (the library says so: SVH_E_STATE)
+            _lib.check(_lib.lib.svh_batchset_decode_read(self._h, 0, None, None, None, None, ctypes.c_void_p(stream or 0)))
+        out = []
+        for k, (m, r) in enumerate(getattr(self, "_decoded", None) or []):
+            scores = np.empty(self.mset.models[m].n, np.float32)
+            path = np.empty(int(self.offsets[r + 1] - self.offsets[r]), np.int32)
+            best, fb = ctypes.c_int64(), ctypes.c_int32()
+            _lib.check(_lib.lib.svh_batchset_decode_read(self._h, k, _p(scores, _f32), ctypes.byref(best), _p(path, _i32),
+                                                         ctypes.byref(fb), ctypes.c_void_p(stream or 0)))
+            out.append((scores, int(best.value), path) + ((bool(fb.value),) if fell_back else ()))
+        return out
+
+    def decode_info(self) -> dict:
+        """Of the last decode (svh_batchset_decode_info): pairs, members (with a pair), grouped (of those,
+        in the set's launches), grouped_pairs, launches, grid / lds_bytes / waves of the forward set
+        launch, fallback_pairs (synchronises), builds."""
+        i = _lib.svh_batchset_decode_info()
+        _lib.check(_lib.lib.svh_batchset_decode_get_info(self._h, ctypes.byref(i)))
+        return {name: getattr(i, name) for name, _ in i._fields_}
+
+    def decode_elapsed_ms(self) -> float:
+        ms = ctypes.c_float()
+        _lib.check(_lib.lib.svh_batchset_decode_elapsed_ms(self._h, ctypes.byref(ms)))
+        return float(ms.value)
+
     def close(self):
         if getattr(self, "_h", None):
             for b in self.members:
